@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Headline benchmark: RAFT (full, raft-things config) training throughput on
 synthetic FlyingChairs-shaped pairs (368x496, 12 iterations, bf16, DDP over
-RCCL), plus Sintel-resolution (1088x436, padded 1088x440) 12-iteration
-inference FPS on rank 0.
+RCCL).  With ``--full`` also Sintel-resolution (1088x436, padded 1088x440)
+12-iteration inference FPS on rank 0; a plain run sets up, warms up, times
+the K steps, writes ``--dump-outputs DIR`` if asked and prints the result
+line (``inference`` is null).
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1
 the driver launches it under torch.distributed.run (one rank per GPU, RCCL).
@@ -15,8 +17,23 @@ line.  ``--device cpu`` runs the same step on CPU ranks over gloo (tests).
 
 value = total image pairs / s over all N GPUs (weak scaling: fixed per-GPU
 batch).  BASELINE.md publishes no training throughput (vs_baseline null for
-the training value); the inference FPS is compared against the paper's
-~10 fps (GTX 1080Ti, 1088x436) as ``inference.vs_baseline``.
+the training value); the ``--full`` inference FPS is compared against the
+paper's ~10 fps (GTX 1080Ti, 1088x436) as ``inference.vs_baseline``.
+
+``--dump-outputs DIR`` writes what the last timed step computed (loss, the
+updated parameters, the eager step's final flow prediction) as float32
+``DIR/<name>.npy``.  Model weights and the synthetic batches are seeded, so
+the inputs are the same from run to run.  By default (``--deterministic
+auto``) a run that dumps takes its steps in deterministic mode
+(runtime/determinism.py: weight gradients reduced in a fixed order instead of
+with fp32 atomics; ``config.deterministic`` in the result line says so), so
+two runs write the same values and two builds can be compared output for
+output; everything but those accumulation epilogues is the code of the
+headline step, and tests/test_determinism_gpu.py ties the two epilogues
+together.  ``--deterministic off --dump-outputs DIR`` dumps the default step
+itself, whose outputs move from run to run (0.2 px in the flow after 25
+steps).  The headline figure comes from runs without ``--dump-outputs``; the
+result line of a dumping run lists the files it wrote as ``dumped``.
 """
 from __future__ import annotations
 
@@ -33,6 +50,7 @@ sys.path.insert(0, HERE)
 
 METRIC = "train image-pairs/sec (node) + Sintel-res inference FPS, RAFT 12 iters"
 BASELINE_INFER_FPS = 10.0  # RAFT paper, GTX 1080Ti, 1088x436
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs writes at most this much in all
 
 
 def parse():
@@ -47,7 +65,19 @@ def parse():
     ap.add_argument("--fp32", action="store_true", help="disable bf16 autocast")
     ap.add_argument("--alternate-corr", action="store_true",
                     help="on-the-fly (memory-efficient) correlation instead of the all-pairs pyramid")
-    ap.add_argument("--no-infer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline training measurement also run the secondary measurements "
+                         "(Sintel-resolution inference FPS on rank 0); a plain run times the training steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(float32): loss, the updated parameters (one flat vector, model.parameters() order) and, "
+                         "for the eager step, the final flow prediction (the graphed step hands back the loss only); "
+                         "see --deterministic")
+    ap.add_argument("--deterministic", default="auto", choices=["auto", "on", "off"],
+                    help="deterministic mode for the steps (runtime/determinism.py; GPU only).  auto: on in a run "
+                         "that dumps its outputs, off otherwise (the headline path); off with --dump-outputs "
+                         "dumps the default atomic-accumulation step, which differs from run to run")
+    ap.add_argument("--no-infer", action="store_true", help="with --full: skip the inference measurement")
     ap.add_argument("--infer-size", type=int, nargs=2, default=[436, 1088])
     ap.add_argument("--infer-reps", type=int, default=20)
     ap.add_argument("--no-graph", action="store_true", help="eager inference instead of hipGraph")
@@ -121,8 +151,17 @@ def main():
         torch.cuda.set_device(dev)
     torch.manual_seed(1234)
 
+    # --deterministic auto: a run that dumps its outputs takes the fixed-order reductions of
+    # train.py --deterministic, so equal inputs give equal files.  The default step sums weight
+    # gradients with fp32 atomics; their order, and through AdamW's sign-like early updates the
+    # weights and flows of later steps, change from run to run by far more than rounding.
+    # ``--deterministic off --dump-outputs DIR`` dumps the default step itself, noise included.
+    det = not cpu and (a.deterministic == "on" or (a.deterministic == "auto" and bool(a.dump_outputs)))
+    if det:
+        from raft_stir_amd.runtime.determinism import set_deterministic
+        set_deterministic(True)
     margs = make_args(small=a.small, mixed_precision=not a.fp32 and not cpu, corr_dtype=a.corr_dtype,
-                      alternate_corr=a.alternate_corr)
+                      alternate_corr=a.alternate_corr, deterministic=det)
     model = RAFT(margs).to(dev)
     if not cpu:
         model = model.to(memory_format=torch.channels_last)
@@ -134,6 +173,7 @@ def main():
     targs = argparse.Namespace(lr=4e-4, wdecay=1e-4, epsilon=1e-8, num_steps=100000)
     H, W = a.size
     pool = DevicePool(4, a.batch, H, W, dev, seed=info.rank * 97)
+    last = {}  # --dump-outputs: the eager step's final flow prediction
 
     if use_graph:
         # the same step, replayed from one hipGraph: the AdamW learning rate lives in
@@ -156,6 +196,8 @@ def main():
             i1, i2, flow, valid = pool.next()
             optimizer.zero_grad(set_to_none=True)
             preds = ddp(i1, i2, iters=a.iters)
+            if a.dump_outputs:
+                last["flow"] = preds[-1]
             loss, _ = sequence_loss(preds, flow, valid, gamma=0.8, sync_metrics=False)
             loss.backward()
             if hasattr(optimizer, "clip_and_step"):  # clip + AdamW, two native launches
@@ -167,6 +209,7 @@ def main():
             return loss
 
     sync = (lambda: None) if cpu else torch.cuda.synchronize
+    loss = torch.zeros((), device=dev)
     for _ in range(a.warmup):
         step()
     rdist.barrier()
@@ -181,8 +224,12 @@ def main():
     ms = 1000.0 * elapsed / max(a.steps, 1)
     pairs_per_s = a.batch * info.world_size * a.steps / elapsed
 
+    dumped = None
+    if info.is_main and a.dump_outputs:
+        dumped = dump_outputs(a.dump_outputs, loss, model, last.get("flow"))
+
     infer = None
-    if info.is_main and not a.no_infer and not cpu:
+    if a.full and info.is_main and not a.no_infer and not cpu:
         infer = bench_inference(model, dev, a)
 
     if info.is_main:
@@ -211,16 +258,39 @@ def main():
                 "corr_pyramid": "fp32" if (a.reference_ops or cpu) else str(model_cfg_pyr(model)),
                 "correlation": "on-the-fly" if a.alternate_corr else "all-pairs",
                 "train_step": "hipgraph" if use_graph else "eager",
+                "deterministic": det,
                 "grad_allreduce": ("none" if info.world_size == 1 else
                                    "rccl: packed update-block buffer + DDP encoder buckets"
                                    if getattr(model.__dict__.get("_fused_train"), "grad_group", None)
                                    else f"{info.backend} DDP buckets"),
             },
             "final_loss": round(float(loss.detach()), 4),
+            "dumped": dumped,
             "inference": infer,
         }
         print(json.dumps(out), flush=True)
     rdist.shutdown()
+
+
+@torch.no_grad()
+def dump_outputs(path, loss, model, flow):
+    """What the last timed step handed back, as float32 ``<name>.npy`` files
+    (33 MB at the default shapes): the loss, every parameter after the step's
+    update and, for the eager step, its last flow prediction."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": loss.detach().reshape(1),
+           "params": torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])}
+    if flow is not None:
+        flow = flow.detach()
+        room = (DUMP_LIMIT_BYTES - 4 * out["params"].numel() - 4) // 4
+        if flow.numel() > room:  # larger --batch / --size: a fixed, seeded sample of the elements
+            idx = torch.randperm(flow.numel(), generator=torch.Generator().manual_seed(0))[:room].sort().values
+            flow = flow.reshape(-1)[idx.to(flow.device)]
+        out["flow_final"] = flow
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+    return sorted(out)
 
 
 @torch.no_grad()

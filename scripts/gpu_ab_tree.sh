@@ -20,7 +20,8 @@ fi
 for rep in $(seq ${REPS:-2}); do
   for arm in base new; do
     if [ $arm = base ]; then D=$BASE; else D=.; fi
-    (cd $D && timeout -k 10 400 python bench.py --steps 30 --warmup 5 --infer-reps 50 ${BENCH_ARGS}) > $OUT/$arm.log 2>&1 \
+    # --full (inference too) where the tree's bench.py has it; older baselines measure both by default
+    (cd $D || exit 1; FULL=$(python bench.py --help | grep -c -- --full > /dev/null && echo --full); timeout -k 10 400 python bench.py $FULL --steps 30 --warmup 5 --infer-reps 50 ${BENCH_ARGS}) > $OUT/$arm.log 2>&1 \
       || { tail -30 $OUT/$arm.log; exit 1; }
     echo "[$arm] $(tail -1 $OUT/$arm.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], (d.get("inference") or {}).get("fps"))')" | tee -a $OUT/ab.txt
   done

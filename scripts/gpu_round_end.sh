@@ -11,10 +11,10 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 $OUT/pytest_gpu.txt
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { tail -20 $OUT/smoke.txt; exit 1; }
 tail -1 $OUT/smoke.txt
-timeout -k 10 400 python bench.py --steps 30 --warmup 5 --infer-reps 50 > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 30 --warmup 5 --infer-reps 50 > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | tee $OUT/bench.jsonl
 for a in "--small" "--fp32" "--alternate-corr" "--small --alternate-corr"; do
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 --infer-reps 30 $a > $OUT/b.log 2>&1 || { tail -20 $OUT/b.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --infer-reps 30 $a > $OUT/b.log 2>&1 || { tail -20 $OUT/b.log; exit 1; }
   tail -1 $OUT/b.log >> $OUT/bench.jsonl
 done
 timeout -k 10 600 python scripts/bench_configs.py --out $OUT/bench_configs.jsonl > $OUT/bench_configs.log 2>&1 || { tail -30 $OUT/bench_configs.log; exit 1; }

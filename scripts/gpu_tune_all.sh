@@ -27,7 +27,7 @@ for k in sorted(set(a) | set(b)):
 PY
 for t in new old new old; do
   if [[ $t == new ]]; then cp $OUT/conv_tuning.json raft_stir_amd/conv_tuning.json; else cp $OUT/conv_tuning_old.json raft_stir_amd/conv_tuning.json; fi
-  timeout -k 10 400 python bench.py --steps 30 --warmup 5 --infer-reps 50 > $OUT/b.log 2>&1 || { tail -20 $OUT/b.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 30 --warmup 5 --infer-reps 50 > $OUT/b.log 2>&1 || { tail -20 $OUT/b.log; exit 1; }
   timeout -k 10 300 python scripts/infer_only.py --small --graph --reps 50 > $OUT/i.log 2>&1 || { tail -20 $OUT/i.log; exit 1; }
   timeout -k 10 300 python scripts/stir_only.py --bf16 --reps 50 > $OUT/s.log 2>&1 || { tail -20 $OUT/s.log; exit 1; }
   echo "[$t] $(tail -1 $OUT/b.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], (d.get("inference") or {}).get("fps"))') | $(tail -1 $OUT/i.log) | $(tail -1 $OUT/s.log)" | tee -a $OUT/ab.txt

@@ -10,6 +10,26 @@ if ROOT not in sys.path:
 REFERENCE = "/root/reference"
 
 
+def _scratch_miopen_db():
+    """MIOpen appends what it finds for conv shapes it has not seen to its user
+    find-db, and the package keeps that file under version control
+    (raft_stir_amd/miopen_db).  A test session (its child processes included)
+    works on a scratch copy, so the tests leave the checkout as they found it.
+    A MIOPEN_USER_DB_PATH set by the user still wins."""
+    if "MIOPEN_USER_DB_PATH" in os.environ:
+        return
+    import atexit
+    import shutil
+    import tempfile
+    dst = tempfile.mkdtemp(prefix="raft_stir_miopen_db_")
+    shutil.copytree(os.path.join(ROOT, "raft_stir_amd", "miopen_db"), dst, dirs_exist_ok=True)
+    os.environ["MIOPEN_USER_DB_PATH"] = dst
+    atexit.register(shutil.rmtree, dst, ignore_errors=True)
+
+
+_scratch_miopen_db()  # before anything imports raft_stir_amd (it only sets a default) or starts MIOpen
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (HIP kernels)")
     config.addinivalue_line("markers", "slow: long-running")
