@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "corr_index.h"
 
 namespace rs {
 namespace lookup {
@@ -73,10 +74,11 @@ __global__ __launch_bounds__(256) void lookup_fwd_kernel(Pyr pyr, int levels,
     const float x = cx + (float)(i - r), y = cy + (float)(j - r);
     const float x0f = floorf(x), y0f = floorf(y);
     const float fx = x - x0f, fy = y - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
+    const int x0 = cell_index(x0f), y0 = cell_index(y0f);
     const int H = pyr.H[l], W = pyr.W[l];
     const PT* row = static_cast<const PT*>(pyr.p[l]) + pix * (size_t)pyr.S[l];
-    float v = 0.f;
+    // a non-finite coordinate (NaN weights, no tap inside) yields NaN, as the reference's sampler does
+    float v = (fx != fx || fy != fy) ? __builtin_nanf("") : 0.f;
     const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
     if (y0 >= 0 && y0 < H) {
       const PT* rr = row + (size_t)y0 * W;
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256) void lookup_bwd_kernel(PyrMut gpyr, int levels
     const float cy = coords[((size_t)b * 2 + 1) * N1 + n] * inv;
     const float bx = floorf(cx), by = floorf(cy);
     const float fx = cx - bx, fy = cy - by;
-    const int X = (int)bx - r + a, Y = (int)by - r + c;
+    const int X = cell_index(bx) - r + a, Y = cell_index(by) - r + c;
     const int H = gpyr.H[l], W = gpyr.W[l];
     if (X < 0 || X >= W || Y < 0 || Y >= H) continue;
     const GT* g = dout + pix * dstride + l * K2;
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(256) void lookup_fwd_wave_kernel(Pyr pyr, int level
     const float bx = floorf(cx), by = floorf(cy);
     fxs[l] = cx - bx;
     fys[l] = cy - by;
-    const int X0 = (int)bx - R, Y0 = (int)by - R;
+    const int X0 = cell_index(bx) - R, Y0 = cell_index(by) - R;
     const int H = lvl_H(pyr, l), W = lvl_W(pyr, l);
     const PT* row = static_cast<const PT*>(lvl_ptr(pyr, l)) + (size_t)pix * lvl_S(pyr, l);
     for (int idx = lane; idx < E2; idx += 64) {
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(256) void lookup_bwd_wave_kernel(PyrMut gpyr, int l
     const float cx = cx0 * inv, cy = cy0 * inv;
     const float bx = floorf(cx), by = floorf(cy);
     const float fx = cx - bx, fy = cy - by;
-    const int X0 = (int)bx - R, Y0 = (int)by - R;
+    const int X0 = cell_index(bx) - R, Y0 = cell_index(by) - R;
     const int H = lvl_H(gpyr, l), W = lvl_W(gpyr, l);
     float* row = lvl_ptr(gpyr, l) + (size_t)pix * lvl_S(gpyr, l);
     const float* G = gs[w][l];  // G[i * D + j], i: x tap, j: y tap

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "corr_index.h"
 
 namespace rs {
 namespace otf {
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(WAVES * 64) void otf_fwd_kernel(const T* __restrict
     const T* f2b = static_cast<const T*>(f2.p[l]) + (size_t)b * H * W * C;
     for (int base = 0; base < E2; base += 8) {
       const int cell = base + grp;
-      const int X = (int)bx - r + cell / E, Y = (int)by - r + cell % E;
+      const int X = cell_index(bx) - r + cell / E, Y = cell_index(by) - r + cell % E;
       float s = 0.f;
       if (cell < E2 && X >= 0 && X < W && Y >= 0 && Y < H) {
         const T* row = f2b + ((size_t)Y * W + X) * C + slot * 4;
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(256) void otf_tile_kernel(const bf16_t* __restrict_
     const float inv = 1.f / (float)(1 << l);
     const float cx = cx0 * inv, cy = cy0 * inv;
     const float bx = floorf(cx), by = floorf(cy);
-    const int X0 = (int)bx - r, Y0 = (int)by - r;
+    const int X0 = cell_index(bx) - r, Y0 = cell_index(by) - r;
     int xmn = qact ? X0 : 0x7fffffff, ymn = qact ? Y0 : 0x7fffffff;
     int xmx = qact ? X0 : -0x7fffffff, ymx = qact ? Y0 : -0x7fffffff;
 #pragma unroll
@@ -218,8 +219,10 @@ __global__ __launch_bounds__(256) void otf_tile_kernel(const bf16_t* __restrict_
       xmx = max(xmx, __shfl_xor(xmx, o, 64));
       ymx = max(ymx, __shfl_xor(ymx, o, 64));
     }
+    // box extents (origins are cell_index values, and a launched tile has at least one active
+    // query, so xmn <= xmx are both window origins: no overflow); BW / BH are used only when tiled
     const int BW = xmx - xmn + E, BH = ymx - ymn + E;
-    const bool tiled = BW * BH <= MAXC;  // identical in every wave
+    const bool tiled = box_fits(BW, BH, MAXC);  // identical in every wave
     const int sx = tiled ? 1 : E, sy = tiled ? BW : 1;
     if (wave == 0 && lane < 16) {
       qoff[lane] = tiled ? (Y0 - ymn) * BW + (X0 - xmn) : 0;
@@ -383,7 +386,7 @@ __global__ __launch_bounds__(WAVES * 64) void otf_bwd_kernel(const T* __restrict
     float* d2b = DET ? nullptr : df2.p[l] + (size_t)b * H * W * C;
     for (int base = 0; base < E2; base += 8) {
       const int cell = base + grp;
-      const int X = (int)bx - r + cell / E, Y = (int)by - r + cell % E;
+      const int X = cell_index(bx) - r + cell / E, Y = cell_index(by) - r + cell % E;
       if (active && cell < E2 && X >= 0 && X < W && Y >= 0 && Y < H) {
         const float gc = gs[wave][cell];
         if (gc != 0.f) {
@@ -491,8 +494,8 @@ __global__ __launch_bounds__(256) void otf_tile_bwd_kernel(const T* __restrict__
       const float inv = 1.f / (float)(1 << l);
       const float cx = coords[((size_t)b * 2 + 0) * N1 + n] * inv, cy = coords[((size_t)b * 2 + 1) * N1 + n] * inv;
       const float bx = floorf(cx), by = floorf(cy);
-      qX0[t] = (int)bx - r;
-      qY0[t] = (int)by - r;
+      qX0[t] = cell_index(bx) - r;
+      qY0[t] = cell_index(by) - r;
       qfx[t] = cx - bx;
       qfy[t] = cy - by;
     }
@@ -506,7 +509,7 @@ __global__ __launch_bounds__(256) void otf_tile_bwd_kernel(const T* __restrict__
         ymn = min(ymn, qY0[q]);
         ymx = max(ymx, qY0[q]);
       }
-    const bool fallback = (xmx - xmn + E) * (ymx - ymn + E) > MAXC;  // identical in every thread
+    const bool fallback = !box_fits(xmx - xmn + E, ymx - ymn + E, MAXC);  // identical in every thread
     const T* f2b = static_cast<const T*>(f2.p[l]) + (size_t)b * H * W * C;
     for (int sub = 0; sub < (fallback ? 16 : 1); ++sub) {
       if (fallback && qn[sub] < 0) continue;  // uniform
@@ -695,8 +698,8 @@ __global__ __launch_bounds__(256) void otf_tile_bwd_mma_kernel(const bf16_t* __r
       const float inv = 1.f / (float)(1 << l);
       const float cx = coords[((size_t)b * 2 + 0) * N1 + n] * inv, cy = coords[((size_t)b * 2 + 1) * N1 + n] * inv;
       const float bx = floorf(cx), by = floorf(cy);
-      qX0[t] = (int)bx - r;
-      qY0[t] = (int)by - r;
+      qX0[t] = cell_index(bx) - r;
+      qY0[t] = cell_index(by) - r;
       qfx[t] = cx - bx;
       qfy[t] = cy - by;
     }
@@ -710,7 +713,7 @@ __global__ __launch_bounds__(256) void otf_tile_bwd_mma_kernel(const bf16_t* __r
         ymn = min(ymn, qY0[q]);
         ymx = max(ymx, qY0[q]);
       }
-    const bool fallback = (xmx - xmn + E) * (ymx - ymn + E) > MAXC;  // identical in every thread
+    const bool fallback = !box_fits(xmx - xmn + E, ymx - ymn + E, MAXC);  // identical in every thread
     const bf16_t* f2b = static_cast<const bf16_t*>(f2.p[l]) + (size_t)b * H * W * C;
     for (int sub = 0; sub < (fallback ? 16 : 1); ++sub) {
       if (fallback && qn[sub] < 0) continue;  // uniform

@@ -9,7 +9,11 @@
 //
 //   stats    : per (group, channel) mean / rstd, group = sample (instance
 //              norm) or the whole batch (batch norm); two-level reduction
-//              (per-block partials -> fp64 finalize), deterministic.
+//              (per-block partials -> fp64 finalize), deterministic.  The
+//              pass also sums x - pivot and its square (pivot: the group's
+//              first pixel): a channel whose mean is large against its
+//              spread (textureless frames), where sum x^2 / n - mean^2
+//              cancels in fp32, takes its statistics from those sums.
 //   apply    : y = act(gamma * (x - mean) * rstd + beta)  [+ residual, ReLU]
 //   backward : S1 = sum g, S2 = sum g*xhat  (same two-level reduction), then
 //              dx = gamma * rstd * (g - S1/N - xhat * S2/N), d(residual).
@@ -23,6 +27,7 @@ namespace rs {
 namespace norm {
 
 constexpr int THREADS = 256;
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
 template <typename T> struct Vec;
 template <> struct Vec<float> {
@@ -122,7 +127,9 @@ struct Running {
 };
 
 // --------------------------------------------------------------- reductions
-// MODE 0: (x, x^2).  MODE 1: (g, g * xhat) with g the gradient reaching the
+// MODE 0: (x, x^2) and, as the second partial set (ws2), (d, d^2) with d = x -
+// pivot, the group's first pixel; each pair {x, d} is one packed add and one
+// packed fma.  MODE 1: (g, g * xhat) with g the gradient reaching the
 // pre-activation a = gamma * xhat + beta.
 // AFF (MODE 1 only): the affine residual's constants and partial set are
 // compiled in only where they are used -- as a run-time branch they held ~50
@@ -162,6 +169,11 @@ __global__ __launch_bounds__(THREADS) void reduce_kernel(Args a) {
       }
     }
   }
+  float piv[VN];
+  f32x2_t pa0[VN], pa1[VN];  // MODE 0: {sum x, sum d}, {sum x^2, sum d^2}
+#pragma unroll
+  for (int i = 0; i < VN; ++i) pa0[i] = pa1[i] = f32x2_t{0.f, 0.f};
+  if (MODE == 0 && row < rows) V::load(static_cast<const T*>(a.x) + (size_t)g * a.P * a.C + col * VN, piv);
   if (row < rows) {
     const T* x = static_cast<const T*>(a.x) + (size_t)b * a.P * a.C;
     const T* dy = static_cast<const T*>(a.dy) + (size_t)b * a.P * a.C;
@@ -191,8 +203,9 @@ __global__ __launch_bounds__(THREADS) void reduce_kernel(Args a) {
         if (MODE == 0) {
 #pragma unroll
           for (int i = 0; i < VN; ++i) {
-            acc0[i] += xv[i];
-            acc1[i] += xv[i] * xv[i];
+            const f32x2_t v = {xv[i], xv[i] - piv[i]};
+            pa0[i] += v;
+            pa1[i] += v * v;
           }
         } else {
           float dv[VN], rv[VN], ev[VN];
@@ -224,9 +237,16 @@ __global__ __launch_bounds__(THREADS) void reduce_kernel(Args a) {
       }
     }
   }
+  if (MODE == 0) {
+#pragma unroll
+    for (int i = 0; i < VN; ++i) {
+      acc0[i] = pa0[i].x; racc0[i] = pa0[i].y;
+      acc1[i] = pa1[i].x; racc1[i] = pa1[i].y;
+    }
+  }
   __shared__ float sm[THREADS * 8 * 2];
   const int rr = row < rows ? row : rows;  // idle threads park outside
-  for (int set = 0; set < (aff ? 2 : 1); ++set) {
+  for (int set = 0; set < (aff || MODE == 0 ? 2 : 1); ++set) {
     if (set) __syncthreads();  // the first set's combine is done with sm
 #pragma unroll
     for (int i = 0; i < VN; ++i) {
@@ -253,12 +273,28 @@ __global__ __launch_bounds__(THREADS) void reduce_kernel(Args a) {
 // Block (g, 8-channel chunk): 32 row-groups of 8 lanes each sum a strided
 // share of the (b, s) partials in fp64, then an LDS tree across the groups
 // (short serial chains: batch-norm groups have B * S partials per channel).
+// MODE 0 takes two partial sets: ws = sums of x and x^2, ws2 = sums of
+// d = x - pivot and d^2, the pivot being the group's first pixel of the channel
+// (xref: the tensor, bf16 when xbf16, P pixels per sample).  The first set
+// gives mean = t0 / n, var = t1 / n - mean^2; from fp32 partials that variance
+// carries an error of about 2^-24 * (the summation's growth) * mean^2, measured
+// in the normalised output as 4.9e-7 * mean^2 / var (7.8e-6 at 16, 1.3e-4 at
+// 256), and a constant channel gets a variance of rounding noise.  A channel
+// with mean^2 > kIllCond * (var + eps) takes the second set instead: mean =
+// pivot + t0 / n, var = t1 / n - (t0 / n)^2 with 1 / n in fp64, no
+// cancellation.  Below the threshold the one-pass error stays under 5.9e-6,
+// about 1e-6 of the normalised output's range of +-5, and the channel keeps
+// the first set's result bit for bit (so do the results of every model whose
+// activations stay below it).
+constexpr double kIllCond = 12.0;
+
 template <int MODE>
 __global__ __launch_bounds__(256) void finalize_kernel(const float* ws, int B, int S, int C, int G,
                                                        float eps, float inv_n, float* o0, float* o1, Running run,
                                                        const float* ws2 = nullptr, float* o2 = nullptr,
-                                                       float* o3 = nullptr) {
-  if (blockIdx.z) {  // the second partial set (MODE 1 with an affine residual)
+                                                       float* o3 = nullptr, const void* xref = nullptr,
+                                                       int xbf16 = 0, int P = 0) {
+  if (MODE == 1 && blockIdx.z) {  // the second partial set (an affine residual's sums)
     ws = ws2;
     o0 = o2;
     o1 = o3;
@@ -267,50 +303,79 @@ __global__ __launch_bounds__(256) void finalize_kernel(const float* ws, int B, i
   const int c = blockIdx.y * 8 + (threadIdx.x & 7);
   const int part = threadIdx.x >> 3;
   const int b0 = G == 1 ? 0 : g, nb = G == 1 ? B : 1;
-  double t0 = 0.0, t1 = 0.0;
-  if (c < C) {
-    // 4 independent partial loads in flight per thread: the chain of one
-    // dependent load per partial made this kernel latency-bound (8 us per
-    // batch-norm call at 512 partials); the summation order is unchanged
-    // within each thread's strided share, so the result stays deterministic
-    const int n = nb * S;
-    for (int i = part; i < n; i += 32 * 4) {
-      float2 v[4];
+  __shared__ double sm[2][256];
+  // channel totals of one partial set, left in sm[.][0..7]
+  auto total = [&](const float* w) {
+    double t0 = 0.0, t1 = 0.0;
+    if (c < C) {
+      // 4 independent partial loads in flight per thread: the chain of one
+      // dependent load per partial made this kernel latency-bound (8 us per
+      // batch-norm call at 512 partials); the summation order is unchanged
+      // within each thread's strided share, so the result stays deterministic
+      const int n = nb * S;
+      for (int i = part; i < n; i += 32 * 4) {
+        float2 v[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int k = i + 32 * u;
-        v[u] = make_float2(0.f, 0.f);
-        if (k < n) {
-          const int b = b0 + k / S, s = k % S;
-          v[u] = *reinterpret_cast<const float2*>(ws + (((size_t)b * S + s) * C + c) * 2);
+        for (int u = 0; u < 4; ++u) {
+          const int k = i + 32 * u;
+          v[u] = make_float2(0.f, 0.f);
+          if (k < n) {
+            const int b = b0 + k / S, s = k % S;
+            v[u] = *reinterpret_cast<const float2*>(w + (((size_t)b * S + s) * C + c) * 2);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          t0 += v[u].x;
+          t1 += v[u].y;
         }
       }
+    }
+    sm[0][threadIdx.x] = t0;
+    sm[1][threadIdx.x] = t1;
+    __syncthreads();
+    for (int st = 128; st >= 8; st >>= 1) {
+      if (threadIdx.x < st) {
+        sm[0][threadIdx.x] += sm[0][threadIdx.x + st];
+        sm[1][threadIdx.x] += sm[1][threadIdx.x + st];
+      }
+      __syncthreads();
+    }
+  };
+  total(ws);
+  double t0 = 0.0, t1 = 0.0, m = 0.0, var = 0.0;
+  if (threadIdx.x < 8) {
+    t0 = sm[0][threadIdx.x];
+    t1 = sm[1][threadIdx.x];
+  }
+  if (MODE == 0) {
+    __shared__ int ill[8];
+    if (threadIdx.x < 8) {
+      m = t0 * inv_n;
+      var = t1 * inv_n - m * m;
+      var = var < 0.0 ? 0.0 : var;
+      ill[threadIdx.x] = c < C && ws2 != nullptr && m * m > kIllCond * (var + (double)eps);
+    }
+    __syncthreads();  // (also: the first totals have been read)
+    int any = 0;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        t0 += v[u].x;
-        t1 += v[u].y;
+    for (int i = 0; i < 8; ++i) any |= ill[i];
+    if (any) {  // block-uniform
+      total(ws2);
+      if (threadIdx.x < 8 && ill[threadIdx.x]) {
+        const size_t po = (size_t)g * P * C + c;
+        const float piv = xbf16 ? bf2f(static_cast<const bf16_t*>(xref)[po]) : static_cast<const float*>(xref)[po];
+        const double in = 1.0 / ((double)nb * P);
+        const double dm = sm[0][threadIdx.x] * in;
+        m = (double)piv + dm;
+        var = sm[1][threadIdx.x] * in - dm * dm;
+        var = var < 0.0 ? 0.0 : var;
       }
     }
   }
-  __shared__ double sm[2][256];
-  sm[0][threadIdx.x] = t0;
-  sm[1][threadIdx.x] = t1;
-  __syncthreads();
-  for (int st = 128; st >= 8; st >>= 1) {
-    if (threadIdx.x < st) {
-      sm[0][threadIdx.x] += sm[0][threadIdx.x + st];
-      sm[1][threadIdx.x] += sm[1][threadIdx.x + st];
-    }
-    __syncthreads();
-  }
   if (threadIdx.x < 8 && c < C) {
-    t0 = sm[0][threadIdx.x];
-    t1 = sm[1][threadIdx.x];
     const int idx = g * C + c;
     if (MODE == 0) {
-      const double m = t0 * inv_n;
-      double var = t1 * inv_n - m * m;
-      var = var < 0.0 ? 0.0 : var;
       const float r = (float)(1.0 / sqrt(var + (double)eps));
       o0[idx] = (float)m;
       o1[idx] = r;
@@ -533,7 +598,7 @@ void norm_set_reduce_blocks(int n) { norm::g_reduce_target = n > 0 ? n : 512; }
 // ------------------------------------------------------------------ launchers
 int norm_ws_floats(int B, int P, int C, bool bf16, bool stats) {
   const int S = norm::pick_splits(B, P, C, bf16 ? 8 : 4, stats);
-  return B * S * C * 2;
+  return B * S * C * 2 * (stats ? 2 : 1);  // statistics: two partial sets
 }
 
 // rm / rv / nbt / rbias: the BatchNorm running update (G == 1; rm null: none)
@@ -545,6 +610,7 @@ void norm_stats_launch(bool bf16, const void* x, int B, int P, int C, int G, flo
   a.B = B; a.P = P; a.C = C; a.G = G;
   a.S = norm::pick_splits(B, P, C, bf16 ? 8 : 4, true);
   a.ws = ws;
+  a.ws2 = ws + (size_t)B * a.S * C * 2;
   dim3 grid(a.S, B);
   if (bf16)
     hipLaunchKernelGGL((norm::reduce_kernel<bf16_t, 0>), grid, dim3(norm::THREADS), 0, s, a);
@@ -553,7 +619,8 @@ void norm_stats_launch(bool bf16, const void* x, int B, int P, int C, int G, flo
   const float inv_n = 1.f / (float)((G == 1 ? (double)B : 1.0) * P);
   const norm::Running run{rm, rv, nbt, rbias, mom, unb};
   hipLaunchKernelGGL(norm::finalize_kernel<0>, dim3(G, cdiv(C, 8)), dim3(256), 0, s, ws, B, a.S,
-                     C, G, eps, inv_n, mean, rstd, run);
+                     C, G, eps, inv_n, mean, rstd, run, a.ws2, (float*)nullptr, (float*)nullptr, x,
+                     (int)bf16, P);
 }
 
 // rnorm (4 pointers or null): the residual is raw and normalised with

@@ -238,6 +238,7 @@ void corr_lookup_backward(const std::vector<Tensor>& gpyr, const Tensor& coords,
   const int B = coords.size(0), H1 = coords.size(2), W1 = coords.size(3);
   int Hs[4], Ws[4], Ss[4];
   check_pyr(gpyr, B, H1 * W1, Hs, Ws, Ss);
+  TORCH_CHECK(radius >= 0 && radius <= 4, "radius must be in [0,4]");
   const int levels = gpyr.size();
   const int D = 2 * radius + 1;
   check_gpu(dout, "dout");
@@ -526,6 +527,13 @@ std::vector<Tensor> convex_upsample_backward(const Tensor& flow, const Tensor& m
 // All inputs are NHWC-contiguous, viewed as (P, channels).
 int64_t pixels(const Tensor& t) { return t.numel() / t.size(-1); }
 
+// a gate operand: on the GPU, contiguous (the kernels index dense rows) and of the state's dtype
+void check_state(const Tensor& t, const Tensor& state, const char* name) {
+  check_gpu(t, name);
+  TORCH_CHECK(t.scalar_type() == state.scalar_type(), name, " must have the state's dtype ", state.scalar_type(),
+              " (got ", t.scalar_type(), ")");
+}
+
 // cn: (B,H,W,hd+cd) contiguous; hx: (B,H,W,>=hd) contiguous; inp: (B,H,W,cd)
 // with unit channel stride and evenly strided pixel rows (contiguous, or a
 // channel window of a wider NHWC buffer: the inference engine's hx slots);
@@ -556,9 +564,10 @@ void context_act(const Tensor& cn, const Tensor& hx, const Tensor& inp, int64_t 
 Tensor context_act_backward(const Tensor& G, const Tensor& hx, const Tensor& inp, int64_t hd) {
   check_gpu(G, "G");
   check_dtype(G, {at::kFloat}, "G");
-  TORCH_CHECK(G.dim() == 4 && hx.dim() == 4 && inp.dim() == 4 && G.is_contiguous() && hx.is_contiguous() &&
-                  inp.is_contiguous() && hx.scalar_type() == inp.scalar_type(),
-              "context_act_backward: contiguous NHWC tensors");
+  check_gpu(hx, "hx");
+  check_dtype(hx, {at::kFloat, at::kBFloat16}, "hx");
+  check_state(inp, hx, "inp");
+  TORCH_CHECK(G.dim() == 4 && hx.dim() == 4 && inp.dim() == 4, "context_act_backward: 4-d NHWC tensors");
   const int64_t cd = inp.size(3);
   TORCH_CHECK(hd > 0 && G.size(3) >= hd + cd && hx.size(3) >= hd && hx.sizes().slice(0, 3) == G.sizes().slice(0, 3) &&
                   inp.sizes().slice(0, 3) == G.sizes().slice(0, 3),
@@ -594,12 +603,11 @@ std::vector<Tensor> gru_gate_zr(const Tensor& zr, const Tensor& h, const Tensor&
 }
 
 std::vector<Tensor> gru_gate_q(const Tensor& q, const Tensor& z, const Tensor& h) {
-  check_gpu(q, "q");
-  check_gpu(z, "z");
   check_gpu(h, "h");
+  check_dtype(h, {at::kFloat, at::kBFloat16}, "h");
+  check_state(q, h, "q");
+  check_state(z, h, "z");
   TORCH_CHECK(q.sizes() == h.sizes() && z.sizes() == h.sizes(), "gru_gate_q: shapes");
-  TORCH_CHECK(q.scalar_type() == h.scalar_type() && z.scalar_type() == h.scalar_type(),
-              "gru_gate_q: dtype mismatch");
   const c10::DeviceGuard guard(h.device());
   Tensor hn = at::empty_like(h), qt = at::empty_like(h);
   rs::gru_gate_q_launch(is_bf16(h), q.data_ptr(), z.data_ptr(), h.data_ptr(), pixels(h),
@@ -610,10 +618,12 @@ std::vector<Tensor> gru_gate_q(const Tensor& q, const Tensor& z, const Tensor& h
 
 std::vector<Tensor> gru_bwd_q(const Tensor& dhn, const Tensor& z, const Tensor& h,
                               const Tensor& qt) {
-  check_gpu(dhn, "dhn");
-  check_gpu(z, "z");
   check_gpu(h, "h");
-  check_gpu(qt, "qt");
+  check_dtype(h, {at::kFloat, at::kBFloat16}, "h");
+  check_state(z, h, "z");
+  check_state(qt, h, "qt");
+  check_gpu(dhn, "dhn");  // the upstream gradient: fp32 or bf16, whatever the state's dtype
+  check_dtype(dhn, {at::kFloat, at::kBFloat16}, "dhn");
   TORCH_CHECK(dhn.sizes() == h.sizes() && z.sizes() == h.sizes() && qt.sizes() == h.sizes(),
               "gru_bwd_q: shapes");
   const c10::DeviceGuard guard(h.device());
@@ -632,15 +642,15 @@ std::vector<Tensor> gru_bwd_q(const Tensor& dhn, const Tensor& z, const Tensor& 
 }
 
 void gru_bwd_r(const Tensor& drhx, const Tensor& h, const Tensor& r, const Tensor& dzr) {
-  check_gpu(drhx, "drhx");
   check_gpu(h, "h");
-  check_gpu(r, "r");
-  check_gpu(dzr, "dzr");
+  check_dtype(h, {at::kFloat, at::kBFloat16}, "h");
+  check_state(drhx, h, "drhx");
+  check_state(r, h, "r");
+  check_state(dzr, h, "dzr");
   const int hd = h.size(-1), cin = drhx.size(-1) - hd;
   const int64_t P = pixels(h);
-  TORCH_CHECK(pixels(drhx) == P && dzr.size(-1) == 2 * hd && pixels(dzr) == P, "gru_bwd_r: shapes");
-  TORCH_CHECK(drhx.scalar_type() == h.scalar_type() && dzr.scalar_type() == h.scalar_type(),
-              "gru_bwd_r: dtype mismatch");
+  TORCH_CHECK(cin >= 0 && pixels(drhx) == P && r.sizes() == h.sizes() && dzr.size(-1) == 2 * hd && pixels(dzr) == P,
+              "gru_bwd_r: shapes");
   const c10::DeviceGuard guard(h.device());
   rs::gru_bwd_r_launch(is_bf16(h), drhx.data_ptr(), h.data_ptr(), r.data_ptr(), P, hd, cin,
                        dzr.data_ptr(), cur_stream());
@@ -649,17 +659,16 @@ void gru_bwd_r(const Tensor& drhx, const Tensor& h, const Tensor& r, const Tenso
 
 std::vector<Tensor> gru_bwd_fin(const Tensor& dhd, const Tensor& drhx, const Tensor& r,
                                 const Tensor& dhx) {
-  check_gpu(dhd, "dhd");
-  check_gpu(drhx, "drhx");
   check_gpu(r, "r");
-  check_gpu(dhx, "dhx");
+  check_dtype(r, {at::kFloat, at::kBFloat16}, "r");
+  check_state(drhx, r, "drhx");
+  check_state(dhx, r, "dhx");
+  check_gpu(dhd, "dhd");
   check_dtype(dhd, {at::kFloat}, "dhd");
   const int hd = r.size(-1), cin = drhx.size(-1) - hd;
   const int64_t P = pixels(r);
-  TORCH_CHECK(pixels(drhx) == P && dhx.sizes() == drhx.sizes() && dhd.sizes() == r.sizes(),
+  TORCH_CHECK(cin >= 0 && pixels(drhx) == P && dhx.sizes() == drhx.sizes() && dhd.sizes() == r.sizes(),
               "gru_bwd_fin: shapes");
-  TORCH_CHECK(drhx.scalar_type() == r.scalar_type() && dhx.scalar_type() == r.scalar_type(),
-              "gru_bwd_fin: dtype mismatch");
   const c10::DeviceGuard guard(r.device());
   auto sz = r.sizes().vec();
   Tensor dh = at::empty_like(r);

@@ -124,6 +124,49 @@ def convex_upsample(flow, mask, factor: int = 8):
     return up.permute(0, 1, 4, 2, 5, 3).reshape(N, 2, factor * H, factor * W)
 
 
+# ConvGRU gate stages (reference core/update.py:16-60; the chain of ops/gru.py),
+# channels-last rows (..., C) in the dtype of the inputs: the oracles of
+# csrc/gru.hip, one function per kernel.
+def gru_gate_zr(zr, h, x):
+    """zr = [z_pre | r_pre] -> z, r, rhx = [r * h | x]."""
+    hd = h.shape[-1]
+    z, r = torch.sigmoid(zr[..., :hd]), torch.sigmoid(zr[..., hd:])
+    return z, r, torch.cat([r * h, x], dim=-1)
+
+
+def gru_gate_q(q, z, h):
+    """q_pre -> h' = (1 - z) h + z q~, q~ = tanh(q_pre)."""
+    qt = torch.tanh(q)
+    return (1 - z) * h + z * qt, qt
+
+
+def gru_bwd_q(dhn, z, h, qt):
+    """d h' -> dq_pre, dz_pre, the direct part of dh."""
+    return dhn * z * (1 - qt * qt), dhn * (qt - h) * z * (1 - z), dhn * (1 - z)
+
+
+def gru_bwd_r(drhx, h, r):
+    """d rhx (the q convolution's input gradient) -> dr_pre."""
+    return drhx[..., :h.shape[-1]] * h * r * (1 - r)
+
+
+def gru_bwd_fin(dhd, drhx, r, dhx):
+    """dh = dh_direct + d(r h) r + dhx[h part]; dx = drhx[x part] + dhx[x part]."""
+    hd = r.shape[-1]
+    return dhd + drhx[..., :hd] * r + dhx[..., :hd], drhx[..., hd:] + dhx[..., hd:]
+
+
+def context_act(cn, hd: int):
+    """cnet output -> (tanh(net), relu(inp)) (reference core/raft.py:108-110)."""
+    return torch.tanh(cn[..., :hd]), torch.relu(cn[..., hd:])
+
+
+def context_act_backward(G, hx, inp, hd: int):
+    """Gradient rows G = [d h | d inp | ...] -> d cnet, from the saved activations."""
+    cd = inp.shape[-1]
+    return torch.cat([G[..., :hd] * (1 - hx[..., :hd] ** 2), G[..., hd:hd + cd] * (inp > 0)], dim=-1)
+
+
 def upflow8(flow, mode: str = "bilinear"):
     size = (8 * flow.shape[2], 8 * flow.shape[3])
     return 8 * F.interpolate(flow, size=size, mode=mode, align_corners=True)
