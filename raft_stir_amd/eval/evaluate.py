@@ -7,7 +7,8 @@ Same functions, iteration counts and metric definitions:
   * ``validate_kitti(model, iters=24)``   -> {'kitti-epe': mean per-image EPE over
     valid px, 'kitti-f1': 100 * mean((epe > 3) & (epe/|gt| > 0.05))}, InputPadder('kitti')
   * ``create_sintel_submission(model, iters=32, warm_start=False, output_path=...)``
-    (.flo per frame, optional forward-interpolated warm start)
+    (.flo per frame, optional forward-interpolated warm start: on the GPU by
+    the HIP kernel of ops.forward_interpolate, on the CPU by the host KD-tree)
   * ``create_kitti_submission(model, iters=24, output_path=...)`` (16-bit PNG)
 
 Engine differences: on GPU each resolution is run through a cached hipGraph
@@ -23,6 +24,7 @@ import os
 import numpy as np
 import torch
 
+from .. import ops
 from ..data import datasets, frame_utils
 from ..utils.geometry import forward_interpolate
 from ..utils.padder import InputPadder
@@ -63,10 +65,15 @@ def _to(dev, *xs):
 
 @torch.no_grad()
 def create_sintel_submission(model, iters=32, warm_start=False, output_path="sintel_submission",
-                             root="datasets/Sintel"):
+                             root="datasets/Sintel", device_warm_start: bool | None = None):
+    """``device_warm_start``: forward-interpolate the warm start with the HIP
+    kernel (ops.forward_interpolate), so the flow never leaves the device;
+    None = whenever the model is on the GPU, False = the host KD-tree path."""
     model.eval()
     run = _Runner(model)
     dev = run.dev
+    if device_warm_start is None:
+        device_warm_start = dev.type == "cuda"
     for dstype in ["clean", "final"]:
         test_dataset = datasets.MpiSintel(split="test", aug_params=None, dstype=dstype, root=root)
         flow_prev, sequence_prev = None, None
@@ -78,7 +85,9 @@ def create_sintel_submission(model, iters=32, warm_start=False, output_path="sin
             image1, image2 = padder.pad(*_to(dev, image1, image2))
             flow_low, flow_pr = run(image1, image2, iters, flow_init=flow_prev)
             flow = padder.unpad(flow_pr[0]).permute(1, 2, 0).cpu().numpy()
-            if warm_start:
+            if warm_start and device_warm_start:
+                flow_prev = ops.forward_interpolate(flow_low)
+            elif warm_start:
                 flow_prev = forward_interpolate(flow_low[0])[None].to(dev)
             output_dir = os.path.join(output_path, dstype, sequence)
             os.makedirs(output_dir, exist_ok=True)

@@ -20,6 +20,9 @@ device the model lives on.
 :class:`PointTrackServer` is the serving path on MI355X: the whole tracker
 (encoders, 12 iterations, upsampling and point sampling) captured once in a
 hipGraph per input shape and replayed per request with the HIP kernels.
+:class:`SequenceTracker` follows points through a whole video on top of it:
+one frame per step, each pair warm-started from the forward-interpolated flow
+of the pair before (ops.forward_interpolate, csrc/forward_interp.hip).
 """
 from __future__ import annotations
 
@@ -177,3 +180,142 @@ class PointTrackServer:
         with torch.cuda.graph(g):
             out = tracker(p, i1, i2)
         return {"graph": g, "p": p, "i1": i1, "i2": i2, "out": out}
+
+
+class SequenceTracker:
+    """Follow points through a video, one frame per :meth:`step`.
+
+    ``step(frame, points)`` on the first frame stores both and returns the
+    points unchanged; every later ``step(frame)`` returns the (1,N,2) positions
+    in the new frame::
+
+        flow_low, flow_up = model(prev, frame, iters, flow_init=init, test_mode=True)
+        points = points + sample_points(flow_up, points)
+        init = ops.forward_interpolate(flow_low)      # warm_start; zeros without
+
+    The first pair of a sequence starts from zeros.  After a step,
+    ``flow_low``, ``flow_up``, ``flow_init`` (the init that step used) and
+    ``next_init`` (the init the next step will use) are readable until the next
+    step.
+
+    On the GPU the model forward, the point sampling and the forward
+    interpolation are one captured hipGraph per (frame shape, N) over static
+    buffers.  A frame is uploaded once: between steps the graph's ``image2``
+    buffer is copied into ``image1`` on the device, and the new init into the
+    ``flow_init`` buffer.  With frames and points already on the device no step
+    synchronises with the host.  On a CPU model the same loop runs eagerly.
+    """
+
+    def __init__(self, model, iters: int = NUMITERS, warm_start: bool = True):
+        self.model = model.eval()
+        self.iters = iters
+        self.warm_start = warm_start
+        self.graphs = {}
+        self._wkey = None
+        self.reset()
+
+    def reset(self):
+        """Forget the previous frame, the points and the init."""
+        self._prev = None      # previous frame (on the GPU: the image2 buffer it was uploaded to)
+        self.points = None
+        self.flow_low = self.flow_up = self.flow_init = self.next_init = None
+
+    @torch.no_grad()
+    def step(self, frame, points=None):
+        if frame.dim() != 4 or frame.shape[0] != 1 or frame.shape[1] != 3:
+            raise ValueError(f"frame must be (1,3,H,W), got {tuple(frame.shape)}")
+        if frame.shape[-2] % 8 or frame.shape[-1] % 8:
+            raise ValueError(f"frame height and width must be multiples of 8, got {tuple(frame.shape[-2:])}")
+        if self._prev is not None and tuple(self._prev.shape) != tuple(frame.shape):
+            raise ValueError(f"frame shape changed within a sequence: {tuple(self._prev.shape)} -> "
+                             f"{tuple(frame.shape)} (call reset())")
+        if points is None:
+            points = self.points
+        if points is None:
+            raise ValueError("the first step of a sequence needs points")
+        if points.dim() != 3 or points.shape[0] != 1 or points.shape[2] != 2:
+            raise ValueError(f"points must be (1,N,2), got {tuple(points.shape)}")
+        dev = next(self.model.parameters()).device
+        if dev.type == "cuda":
+            return self._step_graphed(dev, frame, points)
+        return self._step_eager(dev, frame, points)
+
+    @torch.no_grad()
+    def track(self, frames, points):
+        """frames (T,1,3,H,W) or a list of (1,3,H,W); points (1,N,2) in the
+        first frame -> (T,N,2) trajectory, ``traj[0] == points``."""
+        self.reset()
+        traj = [self.step(frames[0], points)[0].clone()]
+        for t in range(1, len(frames)):
+            traj.append(self.step(frames[t])[0].clone())
+        return torch.stack(traj)
+
+    def _init_like(self, frame, dev):
+        return torch.zeros(1, 2, frame.shape[-2] // 8, frame.shape[-1] // 8, device=dev)
+
+    def _step_eager(self, dev, frame, points):
+        from ..ops import forward_interpolate
+        frame = frame.to(dev, torch.float32)
+        points = points.to(dev, torch.float32)
+        if self._prev is None:
+            self._prev, self.points = frame, points.clone()
+            self.next_init = self._init_like(frame, dev)
+            return self.points
+        self.flow_init = self.next_init
+        self.flow_low, self.flow_up = self.model(self._prev, frame, iters=self.iters,
+                                                 flow_init=self.flow_init, test_mode=True)
+        self.points = points + sample_points(self.flow_up.to(points.dtype), points)
+        self.next_init = (forward_interpolate(self.flow_low) if self.warm_start
+                          else self._init_like(frame, dev))
+        self._prev = frame
+        return self.points
+
+    def _step_graphed(self, dev, frame, points):
+        from ..runtime.weights import refresh_all, weights_key
+        wkey = weights_key(self.model)
+        if self._wkey is not None and wkey != self._wkey:
+            refresh_all(self.model)  # weights moved since capture: re-pack into the captured storage
+        self._wkey = wkey
+        key = (tuple(frame.shape), points.shape[1])
+        st = self.graphs.get(key)
+        if st is None:
+            st = self.graphs[key] = self._capture(dev, frame, points)
+        if self._prev is None:
+            st["i2"].copy_(frame)
+            self._prev, self.points, self.next_init = st["i2"], points.to(dev, torch.float32).clone(), st["zero"]
+            return self.points
+        st["i1"].copy_(self._prev)
+        st["i2"].copy_(frame)
+        st["p"].copy_(points)
+        st["init"].copy_(self.next_init)
+        st["graph"].replay()
+        self._prev, self.points = st["i2"], st["out"].clone()
+        self.flow_low, self.flow_up, self.flow_init = st["lo"], st["up"], st["init"]
+        self.next_init = st["next"] if self.warm_start else st["zero"]
+        return self.points
+
+    def _run(self, st):
+        from ..ops import forward_interpolate
+        lo, up = self.model(st["i1"], st["i2"], iters=self.iters, flow_init=st["init"], test_mode=True)
+        out = st["p"] + sample_points(up.to(st["p"].dtype), st["p"])
+        return lo, up, out, (forward_interpolate(lo) if self.warm_start else None)
+
+    def _capture(self, dev, frame, points):
+        st = {"p": torch.zeros(1, points.shape[1], 2, device=dev),
+              "i1": torch.zeros(tuple(frame.shape), device=dev).contiguous(memory_format=torch.channels_last),
+              "init": self._init_like(frame, dev), "zero": self._init_like(frame, dev)}
+        st["i2"] = torch.zeros_like(st["i1"])
+        st["i1"].copy_(frame)
+        st["i2"].copy_(frame)
+        st["p"].copy_(points)
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._run(st)
+        torch.cuda.current_stream(dev).wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            st["lo"], st["up"], st["out"], st["next"] = self._run(st)
+        st["graph"] = g
+        return st

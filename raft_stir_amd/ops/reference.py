@@ -182,3 +182,35 @@ def sequence_loss_terms(preds, gt, valid, gamma: float, max_flow: float = 400.0)
         w = gamma ** (n - i - 1)
         loss = loss + w * (v[:, None] * (p - gt).abs()).mean()
     return loss, v
+
+
+def forward_interpolate(flow, query_chunk: int = 1024):
+    """Forward interpolation of a (B,2,H,W) fp32 flow for the video warm start
+    (reference core/utils/utils.py:26-54), by the exact rule of
+    csrc/forward_interp.hip: sample s of cell (x, y) moves to the fp32 position
+    (x + dx[s], y + dy[s]); it is valid iff 0 < x1 < W and 0 < y1 < H; every
+    cell takes the flow of the valid sample with the smallest fp32
+    d2 = fl(fl(ex*ex) + fl(ey*ey)), the lowest row-major index among equals
+    (``argmin`` returns the first minimum); an image without a valid sample
+    gives zeros.  Queries go in chunks, so the N x N table never exists."""
+    B, _, H, W = flow.shape
+    N = H * W
+    flow = flow.float()
+    ys, xs = torch.meshgrid(torch.arange(H, device=flow.device), torch.arange(W, device=flow.device), indexing="ij")
+    gx, gy = xs.reshape(-1).float(), ys.reshape(-1).float()
+    inf = torch.tensor(float("inf"), device=flow.device)
+    out = torch.zeros_like(flow)
+    for b in range(B):
+        f = flow[b].reshape(2, N)
+        x1, y1 = gx + f[0], gy + f[1]
+        ok = (x1 > 0) & (x1 < W) & (y1 > 0) & (y1 < H)
+        x1, y1 = torch.where(ok, x1, inf), torch.where(ok, y1, inf)
+        idx = []
+        for q0 in range(0, N, query_chunk):
+            ex = gx[q0:q0 + query_chunk, None] - x1[None]
+            ey = gy[q0:q0 + query_chunk, None] - y1[None]
+            idx.append(torch.argmin(ex * ex + ey * ey, dim=1))
+        got = f[:, torch.cat(idx)].reshape(2, H, W)
+        # without a valid sample every distance is +inf and argmin is meaningless
+        out[b] = torch.where(ok.any(), got, torch.zeros_like(got))
+    return out

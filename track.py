@@ -1,0 +1,67 @@
+#!/usr/bin/env python
+"""Track points through the frames of a folder (STIR-style point tracking on a
+whole sequence, with RAFT's video warm start).
+
+    python track.py --model M [--small --mixed_precision --iters 12 --no_warm_start] \
+        --path demo-frames --points points.txt --out tracks.csv
+
+``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
+CSV has a ``frame,point,x,y`` row for every point in every frame (frame 0 holds
+the given points).  Frames whose size is no multiple of 8 are replicate-padded
+for the model and the positions are reported in the unpadded frame.
+"""
+import argparse
+import csv
+import glob
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from raft_stir_amd.cli_common import add_model_args, default_device, load_image, load_model  # noqa: E402
+from raft_stir_amd.export.pointtrack import SequenceTracker  # noqa: E402
+from raft_stir_amd.utils.padder import InputPadder  # noqa: E402
+
+
+def track(args):
+    dev = default_device()
+    model = load_model(args, dev)
+    images = sorted(glob.glob(os.path.join(args.path, "*.png")) + glob.glob(os.path.join(args.path, "*.jpg")))
+    if len(images) < 2:
+        raise FileNotFoundError(f"at least two frames (*.png, *.jpg) expected in {args.path!r}")
+    pts = np.loadtxt(args.points, dtype=np.float32, ndmin=2)
+    if pts.shape[1] != 2:
+        raise ValueError(f"{args.points}: one 'x y' per line expected")
+    tracker = SequenceTracker(model, iters=args.iters, warm_start=not args.no_warm_start)
+    padder = InputPadder(load_image(images[0], dev).shape)
+    shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
+    points = torch.from_numpy(pts).to(dev)[None] + shift
+    frames = (padder.pad(load_image(f, dev))[0] for f in images)
+    traj = [tracker.step(next(frames), points)]
+    traj += [tracker.step(frame) for frame in frames]
+    traj = (torch.cat(traj) - shift).cpu().numpy()  # (T,N,2)
+    with open(args.out, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["frame", "point", "x", "y"])
+        for t in range(traj.shape[0]):
+            for n in range(traj.shape[1]):
+                w.writerow([t, n, f"{traj[t, n, 0]:.4f}", f"{traj[t, n, 1]:.4f}"])
+    print(f"wrote {traj.shape[0]} frames x {traj.shape[1]} points to {args.out}")
+    return traj
+
+
+if __name__ == "__main__":
+    parser = argparse.ArgumentParser()
+    add_model_args(parser)
+    parser.add_argument("--model", help="restore checkpoint")
+    parser.add_argument("--path", default="demo-frames", help="folder of frames")
+    parser.add_argument("--points", required=True, help="text file, one 'x y' per line")
+    parser.add_argument("--out", default="tracks.csv")
+    parser.add_argument("--small", action="store_true", help="use small model")
+    parser.add_argument("--mixed_precision", action="store_true", help="use mixed precision")
+    parser.add_argument("--iters", type=int, default=12)
+    parser.add_argument("--no_warm_start", action="store_true", help="start every pair from zero flow")
+    track(parser.parse_args())
