@@ -22,7 +22,9 @@ device the model lives on.
 hipGraph per input shape and replayed per request with the HIP kernels.
 :class:`SequenceTracker` follows points through a whole video on top of it:
 one frame per step, each pair warm-started from the forward-interpolated flow
-of the pair before (ops.forward_interpolate, csrc/forward_interp.hip).
+of the pair before (ops.forward_interpolate, csrc/forward_interp.hip); with
+``fb_check`` it also reports a per-point visibility from a forward-backward
+check of the two flow directions (ops.fb_track_points, csrc/fb_check.hip).
 """
 from __future__ import annotations
 
@@ -204,21 +206,48 @@ class SequenceTracker:
     buffer is copied into ``image1`` on the device, and the new init into the
     ``flow_init`` buffer.  With frames and points already on the device no step
     synchronises with the host.  On a CPU model the same loop runs eagerly.
+
+    ``fb_check=True`` adds a visibility to every position.  A step is then::
+
+        lo, up = model(prev, frame, iters, flow_init=init, test_mode=True, bidirectional=True)
+        points, fb_err, visible = ops.fb_track_points(up[0:1], up[1:2], points, *fb_alpha)
+        init = sgn * ops.forward_interpolate(sgn * lo)     # sgn = +1 forward, -1 backward
+
+    still one graph per (frame shape, N).  ``init`` holds both directions,
+    (2,2,h,w).  The backward field's warm start moves every sample against its
+    own vector and carries the vector along: the same constant-velocity
+    assumption as the forward one.  After a step ``fb_err`` (1,N) is the
+    distance by which each point misses its start on the way back (+inf for a
+    point that left the image) and ``visible`` (1,N) the check's verdict; after
+    the first step of a sequence they are zeros and all true.  ``visible`` is
+    per step, not sticky: what to do with a lost point is the caller's policy.
+    ``flow_bw_low``, ``flow_bw_up``, ``flow_bw_init`` and ``next_bw_init`` are
+    the backward direction's counterparts of the forward attributes, which
+    stay (1,2,..) tensors.  :meth:`fb_map` gives the dense check of the last
+    step's fields.
     """
 
-    def __init__(self, model, iters: int = NUMITERS, warm_start: bool = True):
+    def __init__(self, model, iters: int = NUMITERS, warm_start: bool = True, fb_check: bool = False,
+                 fb_alpha=(0.01, 0.5)):
         self.model = model.eval()
         self.iters = iters
         self.warm_start = warm_start
+        self.fb_check = fb_check
+        self.fb_alpha = (float(fb_alpha[0]), float(fb_alpha[1]))
+        if not (self.fb_alpha[0] >= 0 and self.fb_alpha[1] >= 0):
+            raise ValueError(f"fb_alpha must be two numbers >= 0, got {fb_alpha}")
         self.graphs = {}
         self._wkey = None
         self.reset()
 
     def reset(self):
         """Forget the previous frame, the points and the init."""
+        self._next = None      # the init of the next step: (1,2,h,w), or (2,2,h,w) with fb_check
         self._prev = None      # previous frame (on the GPU: the image2 buffer it was uploaded to)
         self.points = None
         self.flow_low = self.flow_up = self.flow_init = self.next_init = None
+        self.flow_bw_low = self.flow_bw_up = self.flow_bw_init = self.next_bw_init = None
+        self.fb_err = self.visible = None
 
     @torch.no_grad()
     def step(self, frame, points=None):
@@ -241,32 +270,82 @@ class SequenceTracker:
         return self._step_eager(dev, frame, points)
 
     @torch.no_grad()
-    def track(self, frames, points):
+    def track(self, frames, points, return_visibility: bool = False):
         """frames (T,1,3,H,W) or a list of (1,3,H,W); points (1,N,2) in the
-        first frame -> (T,N,2) trajectory, ``traj[0] == points``."""
+        first frame -> (T,N,2) trajectory, ``traj[0] == points``.  With
+        ``return_visibility`` (an ``fb_check`` tracker only):
+        ``(traj, visible (T,N) bool, fb_err (T,N))``."""
+        if return_visibility and not self.fb_check:
+            raise ValueError("return_visibility=True needs a tracker built with fb_check=True")
         self.reset()
-        traj = [self.step(frames[0], points)[0].clone()]
-        for t in range(1, len(frames)):
-            traj.append(self.step(frames[t])[0].clone())
+        traj, vis, err = [], [], []
+        for t in range(len(frames)):
+            traj.append(self.step(frames[t], points if t == 0 else None)[0].clone())
+            if return_visibility:
+                vis.append(self.visible[0].clone())
+                err.append(self.fb_err[0].clone())
+        if return_visibility:
+            return torch.stack(traj), torch.stack(vis), torch.stack(err)
         return torch.stack(traj)
 
+    def fb_map(self):
+        """Dense forward-backward check of the last step's full-resolution
+        fields: (err (1,1,H,W), ok (1,1,H,W) bool).  On demand, outside the graph."""
+        if not self.fb_check:
+            raise ValueError("fb_map() needs a tracker built with fb_check=True")
+        if self.flow_up is None:
+            raise ValueError("fb_map() needs a step on a second frame first")
+        from ..ops import fb_consistency
+        return fb_consistency(self.flow_up, self.flow_bw_up, *self.fb_alpha)
+
     def _init_like(self, frame, dev):
-        return torch.zeros(1, 2, frame.shape[-2] // 8, frame.shape[-1] // 8, device=dev)
+        # both directions' inits in one tensor with fb_check: forward first
+        return torch.zeros(2 if self.fb_check else 1, 2, frame.shape[-2] // 8, frame.shape[-1] // 8, device=dev)
+
+    def _first(self, points):
+        """Bookkeeping of the first step of a sequence; ``self._next`` is set."""
+        self.points = points
+        self.next_init = self._next[0:1]
+        if self.fb_check:
+            self.next_bw_init = self._next[1:2]
+            self.fb_err = torch.zeros(points.shape[:2], device=points.device)
+            self.visible = torch.ones(points.shape[:2], dtype=torch.bool, device=points.device)
+        return self.points
+
+    def _publish(self, init, lo, up, nxt):
+        """The per-step attributes: views of the (1 or 2, 2, ..) tensors."""
+        self._next = nxt
+        self.flow_init, self.flow_low, self.flow_up, self.next_init = init[0:1], lo[0:1], up[0:1], nxt[0:1]
+        if self.fb_check:
+            self.flow_bw_init, self.flow_bw_low, self.flow_bw_up, self.next_bw_init = (
+                init[1:2], lo[1:2], up[1:2], nxt[1:2])
+
+    def _forward(self, i1, i2, p, init, sgn):
+        """One pair: (flow_low, flow_up, new points, fb_err, visible, next init)."""
+        from ..ops import fb_track_points, forward_interpolate
+        if not self.fb_check:
+            lo, up = self.model(i1, i2, iters=self.iters, flow_init=init, test_mode=True)
+            out = p + sample_points(up.to(p.dtype), p)
+            return lo, up, out, None, None, (forward_interpolate(lo) if self.warm_start else None)
+        lo, up = self.model(i1, i2, iters=self.iters, flow_init=init, test_mode=True, bidirectional=True)
+        out, err, ok = fb_track_points(up[0:1], up[1:2], p, *self.fb_alpha)
+        # the backward field moves against its own vectors; negation is exact
+        nxt = sgn * forward_interpolate(sgn * lo) if self.warm_start else None
+        return lo, up, out, err, ok, nxt
+
+    def _sgn(self, dev):
+        return torch.tensor([1.0, -1.0], device=dev).view(2, 1, 1, 1) if self.fb_check else None
 
     def _step_eager(self, dev, frame, points):
-        from ..ops import forward_interpolate
         frame = frame.to(dev, torch.float32)
         points = points.to(dev, torch.float32)
         if self._prev is None:
-            self._prev, self.points = frame, points.clone()
-            self.next_init = self._init_like(frame, dev)
-            return self.points
-        self.flow_init = self.next_init
-        self.flow_low, self.flow_up = self.model(self._prev, frame, iters=self.iters,
-                                                 flow_init=self.flow_init, test_mode=True)
-        self.points = points + sample_points(self.flow_up.to(points.dtype), points)
-        self.next_init = (forward_interpolate(self.flow_low) if self.warm_start
-                          else self._init_like(frame, dev))
+            self._prev, self._next = frame, self._init_like(frame, dev)
+            return self._first(points.clone())
+        init = self._next
+        lo, up, self.points, self.fb_err, self.visible, nxt = self._forward(self._prev, frame, points, init,
+                                                                           self._sgn(dev))
+        self._publish(init, lo, up, nxt if self.warm_start else self._init_like(frame, dev))
         self._prev = frame
         return self.points
 
@@ -282,28 +361,27 @@ class SequenceTracker:
             st = self.graphs[key] = self._capture(dev, frame, points)
         if self._prev is None:
             st["i2"].copy_(frame)
-            self._prev, self.points, self.next_init = st["i2"], points.to(dev, torch.float32).clone(), st["zero"]
-            return self.points
+            self._prev, self._next = st["i2"], st["zero"]
+            return self._first(points.to(dev, torch.float32).clone())
         st["i1"].copy_(self._prev)
         st["i2"].copy_(frame)
         st["p"].copy_(points)
-        st["init"].copy_(self.next_init)
+        st["init"].copy_(self._next)
         st["graph"].replay()
         self._prev, self.points = st["i2"], st["out"].clone()
-        self.flow_low, self.flow_up, self.flow_init = st["lo"], st["up"], st["init"]
-        self.next_init = st["next"] if self.warm_start else st["zero"]
+        if self.fb_check:
+            self.fb_err, self.visible = st["err"].clone(), st["ok"].clone()
+        self._publish(st["init"], st["lo"], st["up"], st["next"] if self.warm_start else st["zero"])
         return self.points
 
     def _run(self, st):
-        from ..ops import forward_interpolate
-        lo, up = self.model(st["i1"], st["i2"], iters=self.iters, flow_init=st["init"], test_mode=True)
-        out = st["p"] + sample_points(up.to(st["p"].dtype), st["p"])
-        return lo, up, out, (forward_interpolate(lo) if self.warm_start else None)
+        return self._forward(st["i1"], st["i2"], st["p"], st["init"], st["sgn"])
 
     def _capture(self, dev, frame, points):
         st = {"p": torch.zeros(1, points.shape[1], 2, device=dev),
               "i1": torch.zeros(tuple(frame.shape), device=dev).contiguous(memory_format=torch.channels_last),
-              "init": self._init_like(frame, dev), "zero": self._init_like(frame, dev)}
+              "init": self._init_like(frame, dev), "zero": self._init_like(frame, dev),
+              "sgn": self._sgn(dev)}
         st["i2"] = torch.zeros_like(st["i1"])
         st["i1"].copy_(frame)
         st["i2"].copy_(frame)
@@ -316,6 +394,6 @@ class SequenceTracker:
         torch.cuda.current_stream(dev).wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            st["lo"], st["up"], st["out"], st["next"] = self._run(st)
+            st["lo"], st["up"], st["out"], st["err"], st["ok"], st["next"] = self._run(st)
         st["graph"] = g
         return st

@@ -209,7 +209,23 @@ class RAFT(nn.Module):
         return torch.autocast(device_type="cuda", dtype=torch.bfloat16, enabled=enabled)
 
     # ---------------------------------------------------------------- forward
-    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False):
+    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False,
+                bidirectional=False):
+        """``bidirectional`` (inference only): both directions of the pair from
+        one pass.  The feature encoder runs once on the 2B images as always;
+        its two feature maps, swapped, are the backward direction's correlation
+        inputs, the context encoder runs on both images and the refinement
+        loop at batch 2B.  Returns ``(flow_low, flow_up)`` of batch 2B:
+        ``[:B]`` is image1 -> image2, ``[B:]`` is image2 -> image1;
+        ``flow_init`` is (2B,2,h,w) in the same order."""
+        if bidirectional:
+            if not test_mode:
+                raise ValueError("bidirectional=True requires test_mode=True")
+            if torch.is_grad_enabled():
+                raise ValueError("bidirectional=True is an inference pass: call it under torch.no_grad()")
+            if image1.shape != image2.shape:
+                raise ValueError(f"bidirectional=True needs two images of one shape, got "
+                                 f"{tuple(image1.shape)} and {tuple(image2.shape)}")
         dev = image1.device
         gpu = dev.type == "cuda"
         xin = None
@@ -231,6 +247,12 @@ class RAFT(nn.Module):
             fmt = torch.channels_last if gpu else torch.contiguous_format
             image1 = image1.contiguous(memory_format=fmt)
             image2 = image2.contiguous(memory_format=fmt)
+        # the context encoder's input (and the batch of the refinement loop):
+        # image1, or both images for the bidirectional pass -- on the fused-prep
+        # path that is the feature encoder's input buffer itself
+        cimg = image1
+        if bidirectional:
+            cimg = xin if xin is not None else torch.cat([image1, image2], dim=0)
         hdim, cdim = self.hidden_dim, self.context_dim
         mixed = bool(self.cfg.mixed_precision) and gpu
 
@@ -281,8 +303,8 @@ class RAFT(nn.Module):
                 fmap1, fmap2 = _SplitPair.apply(xf, image1.shape[0])
             elif side is not None:
                 # fnet (main) and cnet (side) stage by stage, interleaved on the host
-                xf = xin if xin is not None else torch.cat([image1, image2], dim=0)
-                xc = image1
+                xf = xin if xin is not None else (cimg if bidirectional else torch.cat([image1, image2], dim=0))
+                xc = cimg
                 ff, fc = self.fnet.stage_fns(), self.cnet.stage_fns()
                 for k in range(max(len(ff), len(fc))):
                     if k < len(ff):
@@ -291,7 +313,7 @@ class RAFT(nn.Module):
                         with torch.cuda.stream(side):
                             xc = fc[k](xc)
                 cnet = xc
-                image1.record_stream(side)  # main-stream block read on side (kept by cnet's backward)
+                cimg.record_stream(side)  # main-stream block read on side (kept by cnet's backward)
                 fmap1, fmap2 = _SplitPair.apply(xf, image1.shape[0])
             else:
                 fmap1, fmap2 = self.fnet([image1, image2])
@@ -301,6 +323,9 @@ class RAFT(nn.Module):
             # (exact products); in fp32 mode it runs the exact fp32 MFMA variant.
             if not (mixed and _ext.use_hip(fmap1)):
                 fmap1, fmap2 = fmap1.float(), fmap2.float()
+            if bidirectional:
+                # backward direction: the same two feature maps, swapped
+                fmap1, fmap2 = torch.cat([fmap1, fmap2], dim=0), torch.cat([fmap2, fmap1], dim=0)
             corr_dtype = torch.bfloat16 if mixed else torch.float32
             block = AlternateCorrBlock if self.cfg.alternate_corr else CorrBlock
             kw = {} if self.cfg.alternate_corr else dict(pyr_dtype=self.cfg.pyr_dtype)
@@ -311,9 +336,9 @@ class RAFT(nn.Module):
                 main.wait_stream(side)
                 cnet = _StreamHandoff.apply(cnet, side)
             elif not fused_enc:
-                cnet = self.cnet(image1)
-            fused_train = not test_mode and FusedTrainEngine.eligible(self, image1, corr_fn)
-            fused_inf = not fused_train and FusedUpdate.eligible(self, image1, corr_fn)
+                cnet = self.cnet(cimg)
+            fused_train = not test_mode and FusedTrainEngine.eligible(self, cimg, corr_fn)
+            fused_inf = not fused_train and FusedUpdate.eligible(self, cimg, corr_fn)
             if (fused_train and not self.cfg.small) or fused_inf:
                 # the fused engines split the context features and apply tanh / relu
                 # themselves, straight into their buffers (context_act)
@@ -323,7 +348,7 @@ class RAFT(nn.Module):
                 net = torch.tanh(net)
                 inp = torch.relu(inp)
 
-            coords0, coords1 = self.initialize_flow(image1)
+            coords0, coords1 = self.initialize_flow(cimg)
             if flow_init is not None:
                 coords1 = coords1 + flow_init
 

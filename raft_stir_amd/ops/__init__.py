@@ -4,7 +4,9 @@ from . import _ext, reference
 from .corr import AllPairsCorr, OnTheFlyCorr, CorrState, to_nhwc, from_nhwc
 from .upsample import convex_upsample, upflow8
 from .warm import forward_interpolate
+from .fb import fb_consistency, fb_track_points
 from . import gru
 
 __all__ = ["_ext", "reference", "AllPairsCorr", "OnTheFlyCorr", "CorrState", "to_nhwc",
-           "from_nhwc", "convex_upsample", "upflow8", "forward_interpolate", "gru"]
+           "from_nhwc", "convex_upsample", "upflow8", "forward_interpolate", "fb_consistency",
+           "fb_track_points", "gru"]

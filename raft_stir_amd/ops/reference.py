@@ -214,3 +214,80 @@ def forward_interpolate(flow, query_chunk: int = 1024):
         # without a valid sample every distance is +inf and argmin is meaningless
         out[b] = torch.where(ok.any(), got, torch.zeros_like(got))
     return out
+
+
+def _fb_sample(f, x, y, dtype):
+    """S(f, x, y) of csrc/fb_check.hip: f (B,2,H,W), x and y (B,K) fp32 ->
+    (u, v), each (B,K) in ``dtype``.  The cell indices and the four weights are
+    fp32, as in the kernel; products and sums with the flow are in ``dtype``."""
+    B, _, H, W = f.shape
+    live = (x > -1) & (x < W) & (y > -1) & (y < H)  # NaN / Inf / huge fail: S = 0
+    zero = torch.zeros_like(x)
+    xs, ys = torch.where(live, x, zero), torch.where(live, y, zero)
+    x0, y0 = torch.floor(xs), torch.floor(ys)
+    wx, wy = xs - x0, ys - y0
+    ux, uy = 1 - wx, 1 - wy
+    xi0, yi0 = x0.long(), y0.long()
+    fd = f.to(dtype).reshape(B, 2, H * W)
+    acc = torch.zeros(B, 2, x.shape[1], dtype=dtype, device=f.device)
+    for dx, dy, w in ((0, 0, ux * uy), (1, 0, wx * uy), (0, 1, ux * wy), (1, 1, wx * wy)):
+        xi, yi = xi0 + dx, yi0 + dy
+        use = live & (w != 0) & (xi >= 0) & (xi < W) & (yi >= 0) & (yi < H)
+        idx = yi.clamp(0, H - 1) * W + xi.clamp(0, W - 1)
+        val = fd.gather(2, idx[:, None].expand(B, 2, -1))
+        # a tap that is not used is not read: 0 * NaN must not leak in
+        acc = acc + torch.where(use[:, None], w.to(dtype)[:, None] * val, torch.zeros_like(val))
+    return acc[:, 0], acc[:, 1]
+
+
+def fb_terms(bw, px, py, u, v, dtype=torch.float32):
+    """The terms of the check rule of csrc/fb_check.hip for starts (px, py)
+    (B,K) fp32 with forward vectors (u, v) in ``dtype``: (target inside (B,K)
+    bool, e2, m2 (B,K) ``dtype``; e2 and m2 mean nothing where not inside)."""
+    _, _, H, W = bw.shape
+    qx, qy = px + u.float(), py + v.float()  # fp32 sums
+    inside = (qx >= 0) & (qx <= W - 1) & (qy >= 0) & (qy <= H - 1)
+    bu, bv = _fb_sample(bw, qx, qy, dtype)
+    e2 = (u + bu) ** 2 + (v + bv) ** 2
+    m2 = u * u + v * v + bu * bu + bv * bv
+    return inside, e2, m2
+
+
+def _fb_check(bw, px, py, u, v, start_ok, alpha1, alpha2, dtype):
+    """err (B,K) ``dtype`` and ok (B,K) bool from fb_terms."""
+    inside, e2, m2 = fb_terms(bw, px, py, u, v, dtype)
+    inside = inside & start_ok
+    inf = torch.full_like(e2, float("inf"))
+    err = torch.where(inside, e2.sqrt(), inf)
+    ok = inside & (e2 <= alpha1 * m2 + alpha2)
+    return err, ok
+
+
+def fb_consistency(flow_fw, flow_bw, alpha1: float = 0.01, alpha2: float = 0.5, dtype=torch.float32):
+    """Dense forward-backward check of two (B,2,H,W) fp32 flows by the rule of
+    csrc/fb_check.hip: every pixel centre follows its forward vector, reads the
+    backward flow where it lands and is ok iff
+    |fw + bw(landing)|^2 <= alpha1 * (|fw|^2 + |bw(landing)|^2) + alpha2.
+    -> err (B,1,H,W) ``dtype`` (+inf for a target outside the image), ok (B,1,H,W) bool."""
+    B, _, H, W = flow_fw.shape
+    fw, bw = flow_fw.float(), flow_bw.float()
+    ys, xs = torch.meshgrid(torch.arange(H, device=fw.device), torch.arange(W, device=fw.device), indexing="ij")
+    px = xs.reshape(1, -1).float().expand(B, -1)
+    py = ys.reshape(1, -1).float().expand(B, -1)
+    f = fw.to(dtype).reshape(B, 2, H * W)
+    err, ok = _fb_check(bw, px, py, f[:, 0], f[:, 1], torch.ones_like(px, dtype=torch.bool), alpha1, alpha2, dtype)
+    return err.reshape(B, 1, H, W), ok.reshape(B, 1, H, W)
+
+
+def fb_track_points(flow_fw, flow_bw, points, alpha1: float = 0.01, alpha2: float = 0.5, dtype=torch.float32):
+    """Point form: points (B,N,2) xy fp32 -> (points + S(fw, points) (B,N,2)
+    ``dtype``, err (B,N) ``dtype``, ok (B,N) bool).  A start outside
+    [0,W-1]x[0,H-1] or non-finite gives ok = 0 and err = +inf; its new position
+    is still the zero-padded sample."""
+    _, _, H, W = flow_fw.shape
+    fw, bw, p = flow_fw.float(), flow_bw.float(), points.float()
+    px, py = p[..., 0], p[..., 1]
+    u, v = _fb_sample(fw, px, py, dtype)
+    start_ok = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
+    err, ok = _fb_check(bw, px, py, u, v, start_ok, alpha1, alpha2, dtype)
+    return p.to(dtype) + torch.stack([u, v], dim=-1), err, ok

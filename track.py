@@ -3,12 +3,16 @@
 whole sequence, with RAFT's video warm start).
 
     python track.py --model M [--small --mixed_precision --iters 12 --no_warm_start] \
-        --path demo-frames --points points.txt --out tracks.csv
+        [--fb_check [--fb_alpha A1 A2]] --path demo-frames --points points.txt --out tracks.csv
 
 ``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
 CSV has a ``frame,point,x,y`` row for every point in every frame (frame 0 holds
 the given points).  Frames whose size is no multiple of 8 are replicate-padded
 for the model and the positions are reported in the unpadded frame.
+
+``--fb_check`` adds the columns ``fb_err,visible``: the forward-backward error
+of the step that led to this row, in pixels, and whether the point passed the
+check ``|fw + bw|^2 <= A1 * (|fw|^2 + |bw|^2) + A2`` (frame 0 holds ``0.0000,1``).
 """
 import argparse
 import csv
@@ -35,20 +39,30 @@ def track(args):
     pts = np.loadtxt(args.points, dtype=np.float32, ndmin=2)
     if pts.shape[1] != 2:
         raise ValueError(f"{args.points}: one 'x y' per line expected")
-    tracker = SequenceTracker(model, iters=args.iters, warm_start=not args.no_warm_start)
+    tracker = SequenceTracker(model, iters=args.iters, warm_start=not args.no_warm_start,
+                              fb_check=args.fb_check, fb_alpha=tuple(args.fb_alpha))
     padder = InputPadder(load_image(images[0], dev).shape)
     shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
     points = torch.from_numpy(pts).to(dev)[None] + shift
     frames = (padder.pad(load_image(f, dev))[0] for f in images)
-    traj = [tracker.step(next(frames), points)]
-    traj += [tracker.step(frame) for frame in frames]
+    traj, err, vis = [], [], []
+    for t, frame in enumerate(frames):
+        traj.append(tracker.step(frame, points if t == 0 else None))
+        if args.fb_check:
+            err.append(tracker.fb_err)
+            vis.append(tracker.visible)
     traj = (torch.cat(traj) - shift).cpu().numpy()  # (T,N,2)
+    if args.fb_check:
+        err, vis = torch.cat(err).cpu().numpy(), torch.cat(vis).cpu().numpy()  # (T,N)
     with open(args.out, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["frame", "point", "x", "y"])
+        w.writerow(["frame", "point", "x", "y"] + (["fb_err", "visible"] if args.fb_check else []))
         for t in range(traj.shape[0]):
             for n in range(traj.shape[1]):
-                w.writerow([t, n, f"{traj[t, n, 0]:.4f}", f"{traj[t, n, 1]:.4f}"])
+                row = [t, n, f"{traj[t, n, 0]:.4f}", f"{traj[t, n, 1]:.4f}"]
+                if args.fb_check:
+                    row += [f"{err[t, n]:.4f}", int(vis[t, n])]
+                w.writerow(row)
     print(f"wrote {traj.shape[0]} frames x {traj.shape[1]} points to {args.out}")
     return traj
 
@@ -64,4 +78,8 @@ if __name__ == "__main__":
     parser.add_argument("--mixed_precision", action="store_true", help="use mixed precision")
     parser.add_argument("--iters", type=int, default=12)
     parser.add_argument("--no_warm_start", action="store_true", help="start every pair from zero flow")
+    parser.add_argument("--fb_check", action="store_true",
+                        help="forward-backward check: adds the CSV columns fb_err,visible")
+    parser.add_argument("--fb_alpha", type=float, nargs=2, default=[0.01, 0.5], metavar=("A1", "A2"),
+                        help="the check's relative and absolute threshold terms")
     track(parser.parse_args())
