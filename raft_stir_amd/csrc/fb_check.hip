@@ -29,60 +29,17 @@
 //   fb_points_kernel  (B,N,2) xy points: (u, v) = S(fw, px, py), new = p + (u, v) always; a start
 //                     outside [0,W-1]x[0,H-1] or non-finite gives ok = 0, err = +inf.  One thread
 //                     per point.
-// Both call fb::check, so the two forms cannot drift apart.  No atomics and no
-// dependence on the launch order: the ops are deterministic.
+// Both call fb::check, so the two forms cannot drift apart; the device
+// functions are in csrc/fb_device.h, which csrc/multi_flow.hip shares.  No
+// atomics and no dependence on the launch order: the ops are deterministic.
 #include "common.h"
+#include "fb_device.h"
 
 namespace rs {
 namespace fb {
 
 constexpr int TILE_X = 32, TILE_Y = 8;
 constexpr int THREADS = 256;
-
-__device__ __forceinline__ void tap(const float* __restrict__ fx, const float* __restrict__ fy, int H, int W,
-                                    int xi, int yi, float w, float& u, float& v) {
-  if (w != 0.f && xi >= 0 && xi < W && yi >= 0 && yi < H) {
-    const int i = yi * W + xi;
-    u += w * fx[i];
-    v += w * fy[i];
-  }
-}
-
-// fx, fy: the two planes of one image
-__device__ __forceinline__ void sample(const float* __restrict__ fx, const float* __restrict__ fy, int H, int W,
-                                       float x, float y, float& u, float& v) {
-  u = 0.f;
-  v = 0.f;
-  if (!(x > -1.f && x < (float)W && y > -1.f && y < (float)H)) return;
-  const float xf = floorf(x), yf = floorf(y);
-  const float wx = x - xf, wy = y - yf;
-  const float ux = 1.f - wx, uy = 1.f - wy;
-  const int x0 = (int)xf, y0 = (int)yf;  // [-1, W-1], [-1, H-1]
-  tap(fx, fy, H, W, x0, y0, __fmul_rn(ux, uy), u, v);
-  tap(fx, fy, H, W, x0 + 1, y0, __fmul_rn(wx, uy), u, v);
-  tap(fx, fy, H, W, x0, y0 + 1, __fmul_rn(ux, wy), u, v);
-  tap(fx, fy, H, W, x0 + 1, y0 + 1, __fmul_rn(wx, wy), u, v);
-}
-
-__device__ __forceinline__ bool inside(float x, float y, int H, int W) {
-  return x >= 0.f && x <= (float)(W - 1) && y >= 0.f && y <= (float)(H - 1);
-}
-
-__device__ __forceinline__ void check(const float* __restrict__ bx, const float* __restrict__ by, int H, int W,
-                                      float px, float py, float u, float v, float a1, float a2, float& err,
-                                      bool& ok) {
-  const float qx = px + u, qy = py + v;
-  err = INFINITY;
-  ok = false;
-  if (!inside(qx, qy, H, W)) return;
-  float bu, bv;
-  sample(bx, by, H, W, qx, qy, bu, bv);
-  const float su = u + bu, sv = v + bv;
-  const float e2 = su * su + sv * sv;
-  const float m2 = u * u + v * v + bu * bu + bv * bv;
-  err = sqrtf(e2);
-  ok = e2 <= a1 * m2 + a2;
-}
 
 __global__ __launch_bounds__(TILE_X* TILE_Y) void fb_dense_kernel(const float* __restrict__ fw,
                                                                    const float* __restrict__ bw, int H, int W,
@@ -117,13 +74,11 @@ __global__ __launch_bounds__(THREADS) void fb_points_kernel(const float* __restr
   const float* bx = bw + b * 2 * plane;
   const size_t p = b * N + n;
   const float px = points[2 * p], py = points[2 * p + 1];
-  float u, v;
-  sample(fx, fx + plane, H, W, px, py, u, v);
-  out[2 * p] = px + u;
-  out[2 * p + 1] = py + v;
-  float e = INFINITY;
-  bool k = false;
-  if (inside(px, py, H, W)) check(bx, bx + plane, H, W, px, py, u, v, a1, a2, e, k);
+  float ox, oy, e;
+  bool k;
+  track_point(fx, bx, plane, H, W, px, py, a1, a2, ox, oy, e, k);
+  out[2 * p] = ox;
+  out[2 * p + 1] = oy;
   err[p] = e;
   ok[p] = k;
 }

@@ -25,6 +25,8 @@ one frame per step, each pair warm-started from the forward-interpolated flow
 of the pair before (ops.forward_interpolate, csrc/forward_interp.hip); with
 ``fb_check`` it also reports a per-point visibility from a forward-backward
 check of the two flow directions (ops.fb_track_points, csrc/fb_check.hip).
+export/multiflow.py ``MultiFlowTracker`` tracks over several time spans at
+once and finds a point again after it was lost.
 """
 from __future__ import annotations
 

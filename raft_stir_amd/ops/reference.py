@@ -291,3 +291,45 @@ def fb_track_points(flow_fw, flow_bw, points, alpha1: float = 0.01, alpha2: floa
     start_ok = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
     err, ok = _fb_check(bw, px, py, u, v, start_ok, alpha1, alpha2, dtype)
     return p.to(dtype) + torch.stack([u, v], dim=-1), err, ok
+
+
+def multi_flow_track_points(flow_fw, flow_bw, starts, start_score, start_visible, active,
+                            alpha1: float = 0.01, alpha2: float = 0.5, track=None):
+    """Multi-delta selection by the rule of csrc/multi_flow.hip.  flows
+    (K,2,H,W), slot k spanning t-D_k -> t and back; starts (K,N,2), start_score
+    (K,N), start_visible (K,N) bool: the tracked state in each slot's start
+    frame; active (K,) bool.  Per slot the candidate is
+    ``track(flow_fw[k:k+1], flow_bw[k:k+1], starts[k:k+1], alpha1, alpha2)``
+    (:func:`fb_track_points` unless given: a GPU caller can pass the HIP op),
+    ``s = start_score + err`` and a slot is eligible iff active, start-visible,
+    ok and ``s < +inf``.  A point takes the eligible slot of smallest ``s`` (the
+    lowest among equals), visible; without one the lowest active slot, not
+    visible; without an active slot ``starts[0]`` and ``start_score[0]`` with
+    err = +inf.  -> (points (1,N,2), score (1,N), visible (1,N) bool, choice
+    (1,N) int32 (-1: none), err (1,N), cand_err (K,N))."""
+    track = fb_track_points if track is None else track
+    K, N = starts.shape[:2]
+    cand, err = [], []
+    ok = []
+    for k in range(K):
+        c, e, o = track(flow_fw[k:k + 1], flow_bw[k:k + 1], starts[k:k + 1], alpha1, alpha2)
+        cand.append(c[0])
+        err.append(e[0])
+        ok.append(o[0])
+    cand, err, ok = torch.stack(cand), torch.stack(err), torch.stack(ok)  # (K,N,2), (K,N), (K,N)
+    score = start_score + err
+    act = active.view(K, 1).expand(K, N)
+    inf = torch.full_like(score, float("inf"))
+    elig = act & start_visible & ok & (score < inf)
+    # argmin returns the first minimum: the lowest slot among equals
+    best = torch.argmin(torch.where(elig, score, inf), dim=0)
+    first = torch.argmax(act.to(torch.uint8), dim=0)  # the lowest active slot
+    any_elig, any_act = elig.any(dim=0), act.any(dim=0)
+    pick = torch.where(any_elig, best, first)  # 0 without an active slot
+    g = pick.view(1, N)
+    none = ~any_act
+    points = torch.where(none.view(N, 1), starts[0], cand.gather(0, g.view(1, N, 1).expand(1, N, 2))[0])
+    out_score = torch.where(none, start_score[0], score.gather(0, g)[0])
+    out_err = torch.where(none, inf[0], err.gather(0, g)[0])
+    choice = torch.where(none, torch.full_like(pick, -1), pick).to(torch.int32)
+    return points[None], out_score[None], any_elig[None], choice[None], out_err[None], err

@@ -3,7 +3,8 @@
 whole sequence, with RAFT's video warm start).
 
     python track.py --model M [--small --mixed_precision --iters 12 --no_warm_start] \
-        [--fb_check [--fb_alpha A1 A2]] --path demo-frames --points points.txt --out tracks.csv
+        [--fb_check [--fb_alpha A1 A2]] [--deltas 1 4 16 inf] \
+        --path demo-frames --points points.txt --out tracks.csv
 
 ``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
 CSV has a ``frame,point,x,y`` row for every point in every frame (frame 0 holds
@@ -13,6 +14,14 @@ for the model and the positions are reported in the unpadded frame.
 ``--fb_check`` adds the columns ``fb_err,visible``: the forward-backward error
 of the step that led to this row, in pixels, and whether the point passed the
 check ``|fw + bw|^2 <= A1 * (|fw|^2 + |bw|^2) + A2`` (frame 0 holds ``0.0000,1``).
+
+``--deltas D ...`` tracks over several time spans at once and lets every point
+take the most reliable one, so that a point lost behind an occluder is found
+again (``export/multiflow.py: MultiFlowTracker``): growing frame distances,
+``inf`` last for the first frame as anchor.  The columns are then
+``frame,point,x,y,fb_err,visible,score,delta``: ``score`` the accumulated
+forward-backward error of the chain that led here (``inf`` for a lost point)
+and ``delta`` the span chosen (0: the anchor, -1: none).
 """
 import argparse
 import csv
@@ -26,8 +35,45 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from raft_stir_amd.cli_common import add_model_args, default_device, load_image, load_model  # noqa: E402
+from raft_stir_amd.export.multiflow import MultiFlowTracker  # noqa: E402
 from raft_stir_amd.export.pointtrack import SequenceTracker  # noqa: E402
 from raft_stir_amd.utils.padder import InputPadder  # noqa: E402
+
+
+def _deltas(words):
+    out = []
+    for w in words:
+        if w.lower() in ("inf", "none", "anchor"):
+            out.append(None)
+        else:
+            out.append(int(w))
+    return tuple(out)
+
+
+def track_multi(args, model, images, pts, dev):
+    """--deltas: MultiFlowTracker and the eight-column CSV."""
+    tracker = MultiFlowTracker(model, iters=args.iters, deltas=_deltas(args.deltas), fb_alpha=tuple(args.fb_alpha),
+                               warm_start=not args.no_warm_start)
+    padder = InputPadder(load_image(images[0], dev).shape)
+    shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
+    points = torch.from_numpy(pts).to(dev)[None] + shift
+    cols = [[], [], [], [], []]
+    for t, f in enumerate(images):
+        traj = tracker.step(padder.pad(load_image(f, dev))[0], points if t == 0 else None)
+        for c, v in zip(cols, (traj, tracker.fb_err, tracker.visible, tracker.score, tracker.delta)):
+            c.append(v)
+    traj, err, vis, score, delta = (torch.cat(c) for c in cols)
+    traj = (traj - shift).cpu().numpy()
+    err, vis, score, delta = (v.cpu().numpy() for v in (err, vis, score, delta))
+    with open(args.out, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["frame", "point", "x", "y", "fb_err", "visible", "score", "delta"])
+        for t in range(traj.shape[0]):
+            for n in range(traj.shape[1]):
+                w.writerow([t, n, f"{traj[t, n, 0]:.4f}", f"{traj[t, n, 1]:.4f}", f"{err[t, n]:.4f}", int(vis[t, n]),
+                            f"{score[t, n]:.4f}", int(delta[t, n])])
+    print(f"wrote {traj.shape[0]} frames x {traj.shape[1]} points to {args.out}")
+    return traj
 
 
 def track(args):
@@ -39,6 +85,8 @@ def track(args):
     pts = np.loadtxt(args.points, dtype=np.float32, ndmin=2)
     if pts.shape[1] != 2:
         raise ValueError(f"{args.points}: one 'x y' per line expected")
+    if args.deltas:
+        return track_multi(args, model, images, pts, dev)
     tracker = SequenceTracker(model, iters=args.iters, warm_start=not args.no_warm_start,
                               fb_check=args.fb_check, fb_alpha=tuple(args.fb_alpha))
     padder = InputPadder(load_image(images[0], dev).shape)
@@ -82,4 +130,7 @@ if __name__ == "__main__":
                         help="forward-backward check: adds the CSV columns fb_err,visible")
     parser.add_argument("--fb_alpha", type=float, nargs=2, default=[0.01, 0.5], metavar=("A1", "A2"),
                         help="the check's relative and absolute threshold terms")
+    parser.add_argument("--deltas", nargs="+", metavar="D",
+                        help="track over these frame distances at once ('inf' last: the first frame as anchor) and "
+                             "recover lost points: the CSV columns become x,y,fb_err,visible,score,delta")
     track(parser.parse_args())
