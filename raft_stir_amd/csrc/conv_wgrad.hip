@@ -756,10 +756,13 @@ void colsum_launch(const void* dy, int ystr, int yoff, int C, int P, float* db, 
 
 int flow_wgrad_blocks(int Bp, int H) { return Bp * cdiv(H, wgrad::FROWS); }
 
+// dynamic LDS of flow_wgrad_kernel: the staged flow rows, [2][FROWS + 6][W + 6] fp32
+size_t flow_wgrad_lds(int W) { return sizeof(float) * 2 * (wgrad::FROWS + 6) * ((size_t)W + 6); }
+
 void flow_wgrad_launch(const float* coords, int Bp, int H, int W, const void* df, int fstr, int Cout, float* dw,
                        float* db, float* part, bool f32, hipStream_t stream) {
   const int blocks = flow_wgrad_blocks(Bp, H);
-  const size_t lds = sizeof(float) * 2 * (wgrad::FROWS + 6) * (W + 6);
+  const size_t lds = flow_wgrad_lds(W);
   if (f32)
     hipLaunchKernelGGL(wgrad::flow_wgrad_kernel<float>, dim3(blocks), dim3(256), lds, stream, coords, Bp, H, W,
                        static_cast<const float*>(df), fstr, Cout, dw, db, part);

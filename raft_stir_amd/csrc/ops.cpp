@@ -490,9 +490,14 @@ Tensor upflow8_backward(const Tensor& g, const Tensor& ah, const Tensor& aw) {
 std::vector<Tensor> convex_upsample_backward(const Tensor& flow, const Tensor& mask,
                                              const Tensor& dup, const c10::optional<Tensor>& dmask_out) {
   check_gpu(flow, "flow");
+  check_dtype(flow, {at::kFloat}, "flow");
   check_gpu(mask, "mask");
+  check_dtype(mask, {at::kFloat, at::kBFloat16}, "mask");
   check_gpu(dup, "grad");
   check_dtype(dup, {at::kFloat, at::kBFloat16}, "grad");
+  TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2, "flow must be (N,2,H,W)");
+  TORCH_CHECK(mask.device() == flow.device() && dup.device() == flow.device(),
+              "convex_upsample_backward: flow, mask and grad must be on one device");
   const int N = flow.size(0), H = flow.size(2), W = flow.size(3);
   TORCH_CHECK(mask.dim() == 4 && mask.size(3) == 576, "mask must be (N,H,W,576)");
   TORCH_CHECK(dup.dim() == 4 && dup.size(0) == N && dup.size(1) == 2 && dup.size(2) == 8 * H &&
@@ -507,7 +512,9 @@ std::vector<Tensor> convex_upsample_backward(const Tensor& flow, const Tensor& m
   Tensor dmask;
   if (dmask_out) {
     dmask = *dmask_out;
-    TORCH_CHECK(dmask.is_cuda() && dmask.is_contiguous() && dmask.scalar_type() == mask.scalar_type() &&
+    TORCH_CHECK(dmask.is_cuda() && dmask.device() == mask.device(),
+                "convex_upsample_backward: dmask_out must be on the mask's device");
+    TORCH_CHECK(dmask.is_contiguous() && dmask.scalar_type() == mask.scalar_type() &&
                     dmask.dim() == 4 && dmask.size(0) == N && dmask.size(1) == H && dmask.size(2) == W &&
                     dmask.size(3) >= 576 && dmask.size(3) % 8 == 0 &&
                     (reinterpret_cast<uintptr_t>(dmask.data_ptr()) & 15) == 0,

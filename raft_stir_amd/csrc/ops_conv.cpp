@@ -104,6 +104,7 @@ int wgrad_splits(const WgradLaunch& L);
 int colsum_blocks(int P);
 void colsum_launch(const void* dy, int ystr, int yoff, int C, int P, float* db, float* part, hipStream_t stream);
 int flow_wgrad_blocks(int Bp, int H);
+size_t flow_wgrad_lds(int W);
 void flow_wgrad_launch(const float* coords, int Bp, int H, int W, const void* df, int fstr, int Cout, float* dw,
                        float* db, float* part, bool f32, hipStream_t stream);
 bool deterministic();
@@ -748,7 +749,8 @@ void flow_wgrad(const Tensor& coords, const Tensor& df, const Tensor& dw, const 
   TORCH_CHECK(Cout <= df.size(3) && Cout <= 128 && dw.numel() == 98 * Cout && dw.scalar_type() == at::kFloat &&
                   db.scalar_type() == at::kFloat,
               "flow_wgrad: dw fp32 [49][2][Cout], db fp32 [Cout]");
-  TORCH_CHECK(W <= 1024, "flow_wgrad: row width <= 1024 (LDS staging)");
+  TORCH_CHECK(rs::flow_wgrad_lds(W) <= 65536, "flow_wgrad: row width ", W, " exceeds the LDS staging (",
+              rs::flow_wgrad_lds(W), " > 65536 bytes)");
   TORCH_CHECK(dw.is_contiguous() && db.is_contiguous(), "flow_wgrad: dw, db contiguous");
   const c10::DeviceGuard guard(coords.device());
   Tensor part;

@@ -10,6 +10,13 @@ the GPU (the fused training engine returns them that way) the loss and the
 metrics are one fused HIP pass forward and the loss gradient one pass
 backward (csrc/loss.hip), instead of ~6 ATen kernels per prediction each
 way plus ~40 for the metrics.
+
+Non-finite predictions.  At a valid pixel a NaN prediction makes both forms of
+the loss NaN.  At a masked pixel they differ on purpose: the composite
+multiplies every pixel by the 0 / 1 mask, so ``0 * NaN`` poisons the loss and
+the gradient, while the fused kernels skip masked pixels without reading their
+predictions: the loss stays finite and the gradient there is exactly 0
+(tests/test_flow_path_gpu.py pins this).
 """
 from __future__ import annotations
 

@@ -9,6 +9,12 @@ extreme inputs are pinned here to the reference, not to the kernels:
 * a non-finite coordinate (+-inf, NaN) turns exactly that pixel into NaN;
 * the per-kernel gate formulas (``ref.gru_*``) chained as ops/gru.py chains
   them reproduce fp64 autograd through ``_gru_step_reference``.
+
+The second half does the same for tests/test_flow_path_gpu.py, whose oracles
+live in tests/flow_path_cases.py: they equal ``ref.convex_upsample``, fp64
+autograd and the composite loss of train/loss.py; the flow encoder's bound
+rejects a kernel without the bf16 hi + lo split; the planted loss magnitudes
+are exact in fp32 and no unplanted pixel sits on a 1 / 3 / 5 px threshold.
 """
 import math
 
@@ -160,3 +166,140 @@ def test_context_act_formulas_equal_autograd():
     want, = torch.autograd.grad(torch.cat([net, inp], -1), cn, G[..., :hd + cd])
     got = ref.context_act_backward(G, net.detach(), inp.detach(), hd)
     torch.testing.assert_close(got, want, atol=1e-14, rtol=1e-14)
+
+
+# ------------------------------------------------------------------ the flow path
+# What the oracles of tests/test_flow_path_gpu.py (tests/flow_path_cases.py) say, and
+# that its bounds discriminate.
+import flow_path_cases as fc  # noqa: E402
+
+
+@pytest.mark.parametrize("N,H,W", [(1, 1, 1), (2, 3, 5)])
+def test_convex_upsample_oracle_equals_reference_and_autograd(N, H, W):
+    g = torch.Generator().manual_seed(0)
+    flow = (30 * torch.randn(N, 2, H, W, generator=g, dtype=torch.float64)).requires_grad_()
+    mask = (3 * torch.randn(N, H, W, 576, generator=g, dtype=torch.float64)).requires_grad_()
+    want = ref.convex_upsample(flow, mask.permute(0, 3, 1, 2).contiguous().view(N, 576, H, W))
+    got, bound = fc.cu_fwd_oracle(flow.detach(), mask.detach())
+    torch.testing.assert_close(got, want.detach(), atol=1e-12, rtol=1e-13)
+    assert bool((bound > 0).all())
+    gup = torch.randn(N, 2, 8 * H, 8 * W, generator=g, dtype=torch.float64)
+    wdf, wdm = torch.autograd.grad(want, (flow, mask), gup)
+    df, bdf, dm, bdm = fc.cu_bwd_oracle(flow.detach(), mask.detach(), gup)
+    torch.testing.assert_close(df, wdf, atol=1e-11, rtol=1e-12)
+    torch.testing.assert_close(dm, wdm, atol=1e-11, rtol=1e-12)
+    assert bool((bdf >= 0).all()) and bool((bdm > 0).all())
+
+
+def test_convex_upsample_planted_logits_stay_finite_in_the_oracle():
+    for dt in (torch.float32, torch.bfloat16):
+        flow, mask = fc.cu_inputs(2, 2, 40, dt, seed=1)
+        assert bool(torch.isinf(mask).any()) and float(mask[torch.isfinite(mask)].max()) >= 9984.0
+        want, bound = fc.cu_fwd_oracle(flow, mask)
+        gup = torch.randn(2, 2, 16, 320, generator=torch.Generator().manual_seed(2))
+        parts = fc.cu_bwd_oracle(flow, mask, gup)
+        assert all(bool(torch.isfinite(t).all()) for t in (want, bound, *parts))
+        # a tap at -inf takes no weight and no gradient
+        dm = parts[2]
+        assert bool((dm[torch.isinf(mask)] == 0).all())
+
+
+def test_flow_head_and_flow_wgrad_oracles_equal_autograd():
+    g = torch.Generator().manual_seed(1)
+    B, H, W, C = 2, 3, 5, 8
+    x = torch.randn(B, H, W, C, generator=g, dtype=torch.float64)
+    w = torch.randn(2, 3, 3, C, generator=g, dtype=torch.float64)
+    bias, src = torch.randn(2, generator=g, dtype=torch.float64), torch.randn(B, 2, H, W, generator=g, dtype=torch.float64)
+    xr = x.permute(0, 3, 1, 2).clone().requires_grad_()
+    y = src + F.conv2d(xr, w.permute(0, 3, 1, 2), bias, padding=1)
+    torch.testing.assert_close(fc.fh_fwd_oracle(x, w, bias, src)[0], y.detach(), atol=1e-13, rtol=1e-13)
+    dflow = torch.randn(B, 2, H, W, generator=g, dtype=torch.float64)
+    dx, = torch.autograd.grad(y, xr, dflow)
+    want = dx.permute(0, 2, 3, 1) * (x > 0)
+    torch.testing.assert_close(fc.fh_dgrad_oracle(dflow, w, x)[0], want, atol=1e-13, rtol=1e-13)
+    # flow_wgrad: dW of conv7x7 in the [49][2][C] layout, accumulated into dw0 / db0
+    flow = 100 * torch.randn(B, 2, H, W, generator=g, dtype=torch.float64)
+    df = torch.randn(B, H, W, C + 3, generator=g, dtype=torch.float64)
+    w7 = torch.zeros(49, 2, C, dtype=torch.float64, requires_grad=True)
+    b7 = torch.zeros(C, dtype=torch.float64, requires_grad=True)
+    out = F.conv2d(flow, fc.fe_conv_weight(w7), b7, padding=3)
+    gw, gb = torch.autograd.grad(out, (w7, b7), df[..., :C].permute(0, 3, 1, 2))
+    dw0, db0 = torch.randn(49, 2, C, generator=g, dtype=torch.float64), torch.randn(C, generator=g, dtype=torch.float64)
+    dw, Sw, db, Sb = fc.fw_oracle(flow, df, dw0, db0)
+    torch.testing.assert_close(dw, dw0 + gw, atol=1e-10, rtol=1e-12)
+    torch.testing.assert_close(db, db0 + gb, atol=1e-10, rtol=1e-12)
+    assert bool((Sw >= (dw - dw0).abs() - 1e-9).all()) and bool((Sb >= (db - db0).abs() - 1e-9).all())
+
+
+@pytest.mark.parametrize("scale", [4.0, 100.0, 400.0])
+def test_flow_encoder_bound_discriminates(scale):
+    """The kernel's three split-bf16 products, in exact arithmetic, stay under the
+    test's bound; the hi * hi product alone (plain bf16 operands) exceeds it > 50x
+    at flow scale 100: dropping the split cannot pass."""
+    coords, flow, w, bias = fc.fe_inputs(2, 13, 21, 128, seed=5, scale=scale)
+    flow[:, :, 6, 10] = 4 * scale  # a spike at 4x the scale
+    pre, A = fc.fe_oracle(flow, w, bias)
+    exact = pre - bias.double()
+    three = (fc.fe_emulate(flow, w, {"hh", "hl", "lh"}) - exact).abs()
+    hi = (fc.fe_emulate(flow, w, {"hh"}) - exact).abs()
+    drop = 3 * 2.0 ** -18 * A  # what the derivation allots to the dropped / rounded terms
+    assert bool((three <= drop).all()), (three / drop).max()
+    r3, rh = (three / (2.0 ** -16 * A)).max().item(), (hi / (2.0 ** -16 * A)).max().item()
+    print(f"scale {scale}: three products {r3:.3f} of the bound, hi only {rh:.1f}x")
+    assert r3 <= 0.75
+    if scale == 100.0:
+        assert rh >= 50.0, rh
+
+
+def test_upflow8_helpers_mirror_the_kernel_file():
+    assert fc.up8_band(1) == 8 and fc.up8_band(62) == 25 and fc.up8_cols_lds(62) == (25 * 62 + 4 * 8 * 62) * 4
+    W = fc.up8_largest_w()
+    assert fc.up8_cols_lds(W) <= 65536 < fc.up8_cols_lds(W + 1) and W >= 256
+    from raft_stir_amd.models.fused_train import _interp_matrix
+    for n in (1, 2, 62, 129):
+        assert torch.equal(fc.interp_matrix(n, 8 * n), _interp_matrix(n, 8 * n, "cpu"))
+    # the oracle is the adjoint of 8 * bilinear upsampling (align_corners)
+    f = torch.zeros(1, 2, 3, 5, dtype=torch.float64, requires_grad=True)
+    g = torch.randn(1, 2, 24, 40, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+    (8 * F.interpolate(f, size=(24, 40), mode="bilinear", align_corners=True)).backward(g)
+    want, _ = fc.up8_oracle(g, fc.interp_matrix(3, 24), fc.interp_matrix(5, 40))
+    torch.testing.assert_close(want, f.grad, atol=1e-5, rtol=1e-5)  # fp32 matrices
+
+
+LOSS_CASES = [(1, 1, 1, 1, 3), (12, 2, 3, 5, 20), (3, 1, 16, 17, 36), (2, 1, 725, 724, 725), (2, 1, 724, 724, 724)]
+
+
+@pytest.mark.parametrize("N,B,H,W,seed", LOSS_CASES)
+def test_loss_oracle_equals_the_composite_and_precondition_holds(N, B, H, W, seed):
+    from raft_stir_amd.train.loss import sequence_loss
+    preds, gt, valid, n = fc.loss_inputs(N, B, H, W, seed=seed)
+    assert n == (12 if H * W >= 12 else 0)
+    for gamma in (0.8, 1.0, 0.0):
+        wl, wm, ok, epe = fc.loss_oracle(preds, gt, valid, gamma)
+        assert fc.loss_precondition(epe, ok, n)
+        loss, m = sequence_loss(list(preds.double().unbind(0)), gt.double(), valid.double(), gamma)
+        assert abs(float(loss) - float(wl)) <= 1e-12 * max(1.0, abs(float(wl)))
+        cnt = max(wm["cnt"], 1)
+        assert abs(m["epe"] - wm["epe"]) <= 1e-12 * max(1.0, wm["epe"])
+        assert [m["1px"], m["3px"], m["5px"]] == [wm["1px"] / cnt, wm["3px"] / cnt, wm["5px"] / cnt]
+    if H * W >= 12:  # every plant is in: what fp64 says about them
+        okp, e = ok.view(B, -1)[0, :n], epe.view(B, -1)[0, :n]
+        assert okp.tolist() == [False, True, True, False, False] + [True] * 7
+        assert [bool(e[5 + i] < k) for i, k in enumerate((1, 1, 3, 3, 5, 5, 1))] == [False, True, False, True, False, True, True]
+    # pred - gt is exact in fp32 wherever the pixel counts
+    d32, d64 = (preds - gt).double(), preds.double() - gt.double()
+    assert torch.equal(d32[:, ok[:, None].expand_as(gt)], d64[:, ok[:, None].expand_as(gt)])
+
+
+def test_loss_planted_magnitudes_are_exact_in_fp32():
+    f = lambda *v: torch.tensor(v, dtype=torch.float32)
+    mag = lambda u, v: torch.sqrt(f(u) * f(u) + f(v) * f(v))
+    fused = lambda u, v: torch.sqrt((f(u).double() * f(u).double() + f(v).double() * f(v).double()).float())  # fma
+    for m in (mag, fused):
+        assert float(m(240.0, 320.0)) == 400.0 and float(m(240.0, fc.BELOW(320.0))) < 400.0
+        for (du, dv), k, inside in zip(fc.EPE_PLANT, (1, 1, 3, 3, 5, 5, 1), (False, True, False, True, False, True, True)):
+            assert (float(m(du, dv)) < k) == inside, (du, dv)
+            assert (math.hypot(du, dv) < k) == inside
+        # one fp32 step inside (3, 4) is invisible to any fp32 evaluation: hence four steps
+        assert float(m(3.0, fc.BELOW(4.0))) == 5.0 and float(m(fc.BELOW(3.0), 4.0)) == 5.0
+    assert fc.BELOW(0.5) < 0.5 and not (math.nan >= 0.5)
