@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <initializer_list>
 
 namespace rs {
 struct ConvLaunch {
@@ -143,6 +144,15 @@ void check_nhwc(const Tensor& t, int B, int H, int W, const char* n, at::ScalarT
   TORCH_CHECK(t.size(0) == B && t.size(1) == H && t.size(2) == W, n, ": spatial shape mismatch");
   TORCH_CHECK(t.scalar_type() == dt, n, ": ", dt, " required");
 }
+
+// Every tensor of an op on the device of its first one (the launch uses that
+// device's stream; a pointer from another GPU would be read as a local address).
+void check_one_device(const char* op, const Tensor& first, std::initializer_list<const Tensor*> rest) {
+  for (const Tensor* t : rest)
+    TORCH_CHECK(t == nullptr || !t->defined() || t->device() == first.device(), op,
+                ": all tensors must be on one device, got ", first.device(), " and ", t->device());
+}
+const Tensor* opt_ptr(const c10::optional<Tensor>& t) { return t ? &*t : nullptr; }
 
 // Encoder-normalisation extra shared by conv_fused / conv_geo / conv3x3_halo / stem_conv:
 //   nscale (fp32, >= round_up(Cout, 4), 16-B aligned; epi EPI_NORM only) with
@@ -512,6 +522,8 @@ void conv_wgrad_impl(const Tensor& dy, int64_t yoff, int64_t Cout, const std::ve
                      at::IntArrayRef seg_off, at::IntArrayRef seg_C, at::IntArrayRef seg_period, int64_t KH,
                      int64_t KW, const Tensor& dw, const c10::optional<Tensor>& db, int64_t bn128, int64_t SY,
                      int64_t SX) {
+  check_one_device("conv_wgrad", dy, {&dw, opt_ptr(db)});
+  for (const auto& t : segs) check_one_device("conv_wgrad", dy, {&t});
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 4 && dy.scalar_type() == at::kBFloat16,
               "conv_wgrad: dy must be contiguous bf16 NHWC");
   const int Bp = dy.size(0), H = dy.size(1), W = dy.size(2);
@@ -598,6 +610,13 @@ void conv_wgrad(const Tensor& dy, int64_t yoff, int64_t Cout, const std::vector<
 void conv_wgrad_strided(const Tensor& dy, int64_t Cout, const std::vector<Tensor>& segs, at::IntArrayRef seg_off,
                         at::IntArrayRef seg_C, int64_t KH, int64_t KW, int64_t SY, int64_t SX, const Tensor& dw,
                         const c10::optional<Tensor>& db) {
+  TORCH_CHECK(dy.dim() == 4 && !segs.empty() && segs[0].dim() == 4 && KH >= 1 && KW >= 1 && SY >= 1 && SX >= 1,
+              "conv_wgrad_strided: dy and the segments must be NHWC");
+  // pad K/2, as the kernel's X pixel (y*SY + ky - KH/2, x*SX + kx - KW/2) assumes
+  const int64_t Hi = segs[0].size(1), Wi = segs[0].size(2);
+  TORCH_CHECK(dy.size(1) == (Hi + 2 * (KH / 2) - KH) / SY + 1 && dy.size(2) == (Wi + 2 * (KW / 2) - KW) / SX + 1,
+              "conv_wgrad_strided: dy grid ", dy.size(1), "x", dy.size(2), " does not match the conv geometry (input ",
+              Hi, "x", Wi, ", kernel ", KH, "x", KW, ", stride ", SY, "x", SX, ")");
   std::vector<int64_t> per;
   for (const auto& t : segs) per.push_back(t.size(0) * t.size(1) * t.size(2));
   conv_wgrad_impl(dy, 0, Cout, segs, seg_off, seg_C, per, KH, KW, dw, db, 0, SY, SX);
@@ -624,6 +643,7 @@ static void check_nhwc_view(const Tensor& t, const char* n) {
 //         [relu](conv(x) + bias) [then relu(. + res)]
 void sconv(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, int64_t stride, int64_t pad,
            bool relu, const Tensor& out, int64_t yoff, const c10::optional<Tensor>& res) {
+  check_one_device("sconv", x, {&w, opt_ptr(bias), &out, opt_ptr(res)});
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat),
               "sconv: x bf16 / fp32 NHWC");
   const int B = x.size(0), Hi = x.size(1), Wi = x.size(2), Cin = x.size(3);
@@ -663,6 +683,7 @@ void sconv(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, 
 // dy (x) im2col(x); x / dy dense NHWC views of the same dtype (bf16 / fp32).
 void sconv_wgrad(const Tensor& dy, const Tensor& x, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
                  const Tensor& dw) {
+  check_one_device("sconv_wgrad", x, {&dy, &dw});
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat),
               "sconv_wgrad: x bf16 / fp32 NHWC");
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 && dy.scalar_type() == x.scalar_type(), "sconv_wgrad: dy dtype");
@@ -696,6 +717,7 @@ void sconv_wgrad(const Tensor& dy, const Tensor& x, int64_t KH, int64_t KW, int6
 }
 
 Tensor enc_wgrad(const Tensor& dy, const Tensor& x) {
+  check_one_device("enc_wgrad", x, {&dy});
   check_nhwc_view(dy, "enc_wgrad dy");
   check_nhwc_view(x, "enc_wgrad x");
   const int B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = dy.size(3);
@@ -822,6 +844,7 @@ void conv3x3_halo(const Tensor& x, const Tensor& w, const Tensor& y, int64_t cin
                   const c10::optional<Tensor>& nscale,
                   const c10::optional<Tensor>& nshift, const c10::optional<Tensor>& res, bool relu,
                   bool accumulate) {
+  check_one_device("conv3x3_halo", x, {&w, &y, opt_ptr(nscale), opt_ptr(nshift), opt_ptr(res)});
   TORCH_CHECK(x.dim() == 4, "conv3x3_halo: x must be NHWC");
   const int B = x.size(0), H = x.size(1), W = x.size(2);
   check_nhwc(x, B, H, W, "conv3x3_halo: x");
@@ -869,6 +892,7 @@ void conv3x3_halo(const Tensor& x, const Tensor& w, const Tensor& y, int64_t cin
 //   bias = shift, relu).
 void stem_conv(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, const Tensor& out, int64_t Cout,
                int64_t epi, const c10::optional<Tensor>& nscale, bool relu) {
+  check_one_device("stem_conv", x, {&w, opt_ptr(bias), &out, opt_ptr(nscale)});
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4 && x.size(3) == 3 &&
                   (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
               "stem_conv: x must be a contiguous NHWC [B,H,W,3] fp32 / bf16 image");
@@ -904,6 +928,7 @@ void stem_conv(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bi
 // dW (fp32 [Cout][3][7][7]) of the stem conv from dy (NHWC bf16 [B, Ho, Wo, >= Cout],
 // contiguous) and the image x: deterministic (per-block partials, ordered sum).
 void stem_wgrad(const Tensor& x, const Tensor& dy, int64_t Cout, const Tensor& dw) {
+  check_one_device("stem_wgrad", x, {&dy, &dw});
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4 && x.size(3) == 3 &&
                   (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
               "stem_wgrad: x must be a contiguous NHWC [B,H,W,3] image");
