@@ -227,10 +227,23 @@ class SequenceTracker:
     the backward direction's counterparts of the forward attributes, which
     stay (1,2,..) tensors.  :meth:`fb_map` gives the dense check of the last
     step's fields.
+
+    ``cache_features=True`` encodes every frame once instead of twice (as
+    ``image2``, and one step later as ``image1``): the tracker keeps
+    ``model.encode``'s output of the previous frame in a two-row ring on the
+    device and a step is ``model.encode(frame)`` at batch 1,
+    ``ops.feature_ring_step`` (store the new features, gather the pair) and
+    ``model.refine`` on the gathered features, with or without ``fb_check``;
+    the rest of the step is the same.  Still one graph per (frame shape, N),
+    beside a small one per frame shape that encodes a sequence's first frame;
+    the ring belongs to the frame shape, so N may change within a sequence as
+    without the cache.  The flows
+    differ from the uncached tracker's only by the batch size at which the
+    encoders ran.
     """
 
     def __init__(self, model, iters: int = NUMITERS, warm_start: bool = True, fb_check: bool = False,
-                 fb_alpha=(0.01, 0.5)):
+                 fb_alpha=(0.01, 0.5), cache_features: bool = False):
         self.model = model.eval()
         self.iters = iters
         self.warm_start = warm_start
@@ -238,12 +251,17 @@ class SequenceTracker:
         self.fb_alpha = (float(fb_alpha[0]), float(fb_alpha[1]))
         if not (self.fb_alpha[0] >= 0 and self.fb_alpha[1] >= 0):
             raise ValueError(f"fb_alpha must be two numbers >= 0, got {fb_alpha}")
+        self.cache_features = bool(cache_features)
+        if self.cache_features and not (hasattr(model, "encode") and hasattr(model, "refine")):
+            raise ValueError("cache_features=True needs a model with encode() and refine()")
         self.graphs = {}
+        self._features = {}  # cache_features: frame shape -> the feature ring and the first frame's graph
         self._wkey = None
         self.reset()
 
     def reset(self):
         """Forget the previous frame, the points and the init."""
+        self._t = 0            # frames seen (cache_features: the ring row is t % 2)
         self._next = None      # the init of the next step: (1,2,h,w), or (2,2,h,w) with fb_check
         self._prev = None      # previous frame (on the GPU: the image2 buffer it was uploaded to)
         self.points = None
@@ -267,6 +285,8 @@ class SequenceTracker:
         if points.dim() != 3 or points.shape[0] != 1 or points.shape[2] != 2:
             raise ValueError(f"points must be (1,N,2), got {tuple(points.shape)}")
         dev = next(self.model.parameters()).device
+        if self.cache_features:
+            return self._step_cached(dev, frame, points)
         if dev.type == "cuda":
             return self._step_graphed(dev, frame, points)
         return self._step_eager(dev, frame, points)
@@ -324,12 +344,18 @@ class SequenceTracker:
 
     def _forward(self, i1, i2, p, init, sgn):
         """One pair: (flow_low, flow_up, new points, fb_err, visible, next init)."""
-        from ..ops import fb_track_points, forward_interpolate
         if not self.fb_check:
             lo, up = self.model(i1, i2, iters=self.iters, flow_init=init, test_mode=True)
+        else:
+            lo, up = self.model(i1, i2, iters=self.iters, flow_init=init, test_mode=True, bidirectional=True)
+        return self._follow(lo, up, p, sgn)
+
+    def _follow(self, lo, up, p, sgn):
+        """The points through the flows of one pair, and the next init."""
+        from ..ops import fb_track_points, forward_interpolate
+        if not self.fb_check:
             out = p + sample_points(up.to(p.dtype), p)
             return lo, up, out, None, None, (forward_interpolate(lo) if self.warm_start else None)
-        lo, up = self.model(i1, i2, iters=self.iters, flow_init=init, test_mode=True, bidirectional=True)
         out, err, ok = fb_track_points(up[0:1], up[1:2], p, *self.fb_alpha)
         # the backward field moves against its own vectors; negation is exact
         nxt = sgn * forward_interpolate(sgn * lo) if self.warm_start else None
@@ -399,3 +425,106 @@ class SequenceTracker:
             st["lo"], st["up"], st["out"], st["err"], st["ok"], st["next"] = self._run(st)
         st["graph"] = g
         return st
+
+    # ---------------------------------------------------------- cache_features
+    def _run_first(self, ft):
+        """The first frame of a sequence: encoded into row 0.  The first call
+        for a frame shape allocates the ring and the gathered batch from the
+        features' shapes and dtype."""
+        from ..ops import to_nhwc
+        f, c = self.model.encode(ft["frame"])
+        f, c = to_nhwc(f), to_nhwc(c)
+        if "ring_f" not in ft:
+            if f.dtype != c.dtype:
+                raise ValueError(f"cache_features: encode() returned {f.dtype} features and {c.dtype} context")
+            ft["ring_f"], ft["ring_c"] = f.new_zeros((2,) + tuple(f.shape[1:])), c.new_zeros((2,) + tuple(c.shape[1:]))
+            ft["x"], ft["ctx"] = f.new_zeros((3,) + tuple(f.shape[1:])), c.new_zeros((2,) + tuple(c.shape[1:]))
+        ft["ring_f"][0].copy_(f[0])
+        ft["ring_c"][0].copy_(c[0])
+
+    def _run_cached(self, st):
+        from ..ops import feature_ring_step, from_nhwc, to_nhwc
+        ft = st["features"]
+        f, c = self.model.encode(ft["frame"])
+        feature_ring_step(ft["ring_f"], ft["ring_c"], to_nhwc(f), to_nhwc(c), ft["idx"], ft["x"], ft["ctx"])
+        x, ctx = from_nhwc(ft["x"]), from_nhwc(ft["ctx"])
+        if self.fb_check:
+            lo, up = self.model.refine(x[:2], x[1:], ctx, iters=self.iters, flow_init=st["init"])
+        else:
+            lo, up = self.model.refine(x[0:1], x[1:2], ctx[0:1], iters=self.iters, flow_init=st["init"])
+        return self._follow(lo, up, st["p"], st["sgn"])
+
+    @staticmethod
+    def _graphed(dev, fn):
+        """fn() twice on a side stream, then captured: (graph, fn's outputs)."""
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                fn()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = fn()
+        return g, out
+
+    def _step_cached(self, dev, frame, points):
+        """The feature ring belongs to the frame shape, so that it outlives a
+        change of N within a sequence; the step's graph and its points and
+        init buffers belong to (frame shape, N), as without the cache."""
+        gpu = dev.type == "cuda"
+        if gpu:
+            from ..runtime.weights import refresh_all, weights_key
+            wkey = weights_key(self.model)
+            if self._wkey is not None and wkey != self._wkey:
+                refresh_all(self.model)  # weights moved since capture: re-pack into the captured storage
+            self._wkey = wkey
+        shape = tuple(frame.shape)
+        ft = self._features.get(shape)
+        if ft is None:
+            fmt = torch.channels_last if gpu else torch.contiguous_format
+            ft = self._features[shape] = {
+                "frame": torch.zeros(shape, device=dev).contiguous(memory_format=fmt),
+                # [source row, row written] of an odd and of an even step: frame t lives in row t % 2
+                "idx_table": torch.tensor([[0, 1], [1, 0]], dtype=torch.int32, device=dev),
+                "idx": torch.tensor([0, 1], dtype=torch.int32, device=dev), "graph0": None}
+        ft["frame"].copy_(frame)
+        if self._prev is None:
+            if gpu and ft["graph0"] is None:
+                ft["graph0"], _ = self._graphed(dev, lambda: self._run_first(ft))
+            if gpu:
+                ft["graph0"].replay()
+            else:
+                self._run_first(ft)
+            self._prev, self._next, self._t = ft["frame"], self._zero_cached(dev, frame), 1
+            return self._first(points.to(dev, torch.float32).clone())
+        key = (shape, points.shape[1], "cache_features")
+        st = self.graphs.get(key)
+        if st is None:
+            st = self.graphs[key] = {"p": torch.zeros(1, points.shape[1], 2, device=dev), "features": ft,
+                                     "init": self._init_like(frame, dev), "zero": self._zero_cached(dev, frame),
+                                     "sgn": self._sgn(dev), "graph": None}
+        ft["idx"].copy_(ft["idx_table"][(self._t - 1) % 2])
+        st["p"].copy_(points)
+        st["init"].copy_(self._next)
+        if gpu and st["graph"] is None:
+            # captured on the step's own inputs: the warm-up runs write the ring row that this step writes
+            st["graph"], st["outs"] = self._graphed(dev, lambda: self._run_cached(st))
+        if gpu:
+            st["graph"].replay()
+            lo, up, out, err, ok, nxt = st["outs"]
+        else:
+            lo, up, out, err, ok, nxt = self._run_cached(st)
+        self._t += 1
+        self.points = out.clone()
+        if self.fb_check:
+            self.fb_err, self.visible = err.clone(), ok.clone()
+        self._publish(st["init"], lo, up, nxt if self.warm_start else st["zero"])
+        return self.points
+
+    def _zero_cached(self, dev, frame):
+        """One zero init per frame shape (never written)."""
+        ft = self._features[tuple(frame.shape)]
+        if "zero" not in ft:
+            ft["zero"] = self._init_like(frame, dev)
+        return ft["zero"]

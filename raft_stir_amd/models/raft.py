@@ -184,18 +184,23 @@ class RAFT(nn.Module):
 
     def initialize_flow(self, img):
         N, _, H, W = img.shape
-        if img.device.type != "cuda" or torch.jit.is_tracing():
-            c0 = ref.coords_grid(N, H // 8, W // 8, device=img.device)
-            c1 = ref.coords_grid(N, H // 8, W // 8, device=img.device)
+        return self._coords(N, H // 8, W // 8, img.device)
+
+    @staticmethod
+    def _coords(N, h, w, device):
+        """The pixel-coordinate grids (coords0, coords1) of N (h, w) fields."""
+        if device.type != "cuda" or torch.jit.is_tracing():
+            c0 = ref.coords_grid(N, h, w, device=device)
+            c1 = ref.coords_grid(N, h, w, device=device)
             return c0, c1
         # one cached (1, 2, h, w) grid per shape, expanded into two fresh
         # tensors: two copy kernels per forward instead of eight (arange x4,
         # stack, repeat); not cached while a hipGraph is being captured (its
         # memory would belong to the graph's pool)
-        key = (H // 8, W // 8, img.device)
+        key = (h, w, device)
         g = _GRID_CACHE.get(key)
         if g is None:
-            g = ref.coords_grid(1, H // 8, W // 8, device=img.device)
+            g = ref.coords_grid(1, h, w, device=device)
             if not torch.cuda.is_current_stream_capturing():
                 _GRID_CACHE[key] = g
         shape = (N,) + tuple(g.shape[1:])
@@ -228,32 +233,13 @@ class RAFT(nn.Module):
                                  f"{tuple(image1.shape)} and {tuple(image2.shape)}")
         dev = image1.device
         gpu = dev.type == "cuda"
-        xin = None
-        if (gpu and _FUSED_PREP and image1.dtype == torch.float32 and image2.dtype == torch.float32
-                and image1.shape == image2.shape and not (image1.requires_grad or image2.requires_grad)):
-            # one kernel per image: x * 2/255 - 1 written straight into the two
-            # halves of ONE channels-last buffer -- the feature encoder's batched
-            # input (no separate scale / shift / layout-copy / cat kernels)
-            B = image1.shape[0]
-            xin = torch.empty((2 * B,) + tuple(image1.shape[1:]), device=dev,
-                              memory_format=torch.channels_last)
-            m1 = torch.tensor(-1.0)
-            torch.add(m1, image1, alpha=2.0 / 255.0, out=xin[:B])
-            torch.add(m1, image2, alpha=2.0 / 255.0, out=xin[B:])
-            image1, image2 = xin[:B], xin[B:]
-        else:
-            image1 = 2 * (image1 / 255.0) - 1.0
-            image2 = 2 * (image2 / 255.0) - 1.0
-            fmt = torch.channels_last if gpu else torch.contiguous_format
-            image1 = image1.contiguous(memory_format=fmt)
-            image2 = image2.contiguous(memory_format=fmt)
+        xin, (image1, image2) = self._normalise([image1, image2], gpu)
         # the context encoder's input (and the batch of the refinement loop):
         # image1, or both images for the bidirectional pass -- on the fused-prep
         # path that is the feature encoder's input buffer itself
         cimg = image1
         if bidirectional:
             cimg = xin if xin is not None else torch.cat([image1, image2], dim=0)
-        hdim, cdim = self.hidden_dim, self.context_dim
         mixed = bool(self.cfg.mixed_precision) and gpu
 
         # ONE autocast region for the whole forward: autocast caches the bf16
@@ -304,16 +290,7 @@ class RAFT(nn.Module):
             elif side is not None:
                 # fnet (main) and cnet (side) stage by stage, interleaved on the host
                 xf = xin if xin is not None else (cimg if bidirectional else torch.cat([image1, image2], dim=0))
-                xc = cimg
-                ff, fc = self.fnet.stage_fns(), self.cnet.stage_fns()
-                for k in range(max(len(ff), len(fc))):
-                    if k < len(ff):
-                        xf = ff[k](xf)
-                    if k < len(fc):
-                        with torch.cuda.stream(side):
-                            xc = fc[k](xc)
-                cnet = xc
-                cimg.record_stream(side)  # main-stream block read on side (kept by cnet's backward)
+                xf, cnet = self._encode_overlapped(xf, cimg, side)
                 fmap1, fmap2 = _SplitPair.apply(xf, image1.shape[0])
             else:
                 fmap1, fmap2 = self.fnet([image1, image2])
@@ -326,80 +303,192 @@ class RAFT(nn.Module):
             if bidirectional:
                 # backward direction: the same two feature maps, swapped
                 fmap1, fmap2 = torch.cat([fmap1, fmap2], dim=0), torch.cat([fmap2, fmap1], dim=0)
-            corr_dtype = torch.bfloat16 if mixed else torch.float32
-            block = AlternateCorrBlock if self.cfg.alternate_corr else CorrBlock
-            kw = {} if self.cfg.alternate_corr else dict(pyr_dtype=self.cfg.pyr_dtype)
-            corr_fn = block(fmap1, fmap2, num_levels=self.cfg.corr_levels,
-                            radius=self.cfg.corr_radius, out_dtype=corr_dtype, **kw)
+            corr_fn = self._corr_block(fmap1, fmap2, mixed)
 
             if side is not None:
                 main.wait_stream(side)
                 cnet = _StreamHandoff.apply(cnet, side)
             elif not fused_enc:
                 cnet = self.cnet(cimg)
-            fused_train = not test_mode and FusedTrainEngine.eligible(self, cimg, corr_fn)
-            fused_inf = not fused_train and FusedUpdate.eligible(self, cimg, corr_fn)
-            if (fused_train and not self.cfg.small) or fused_inf:
-                # the fused engines split the context features and apply tanh / relu
-                # themselves, straight into their buffers (context_act)
-                net, inp = cnet, None
+            return self._update(cnet, corr_fn, cimg, flow_init, iters, test_mode, dparams)
+
+    # ----------------------------------------------- the pieces forward is made of
+    @staticmethod
+    def _normalise(images, gpu):
+        """x * 2/255 - 1 of (B,3,H,W) images of one shape -> (the batch of all
+        of them as one buffer, or None; the scaled images).  On the GPU the
+        images are channels-last."""
+        first = images[0]
+        if (gpu and _FUSED_PREP and all(im.dtype == torch.float32 and im.shape == first.shape
+                                        and not im.requires_grad for im in images)):
+            # one kernel per image: x * 2/255 - 1 written straight into its
+            # part of ONE channels-last buffer -- the feature encoder's batched
+            # input (no separate scale / shift / layout-copy / cat kernels)
+            B = first.shape[0]
+            xin = torch.empty((len(images) * B,) + tuple(first.shape[1:]), device=first.device,
+                              memory_format=torch.channels_last)
+            m1 = torch.tensor(-1.0)
+            parts = [xin[k * B:(k + 1) * B] for k in range(len(images))]
+            for im, out in zip(images, parts):
+                torch.add(m1, im, alpha=2.0 / 255.0, out=out)
+            return xin, parts
+        fmt = torch.channels_last if gpu else torch.contiguous_format
+        scaled = [2 * (im / 255.0) - 1.0 for im in images]
+        return None, [im.contiguous(memory_format=fmt) for im in scaled]
+
+    def _encode_overlapped(self, xf, xc, side):
+        """fnet on xf (current stream) and cnet on xc (``side``) stage by
+        stage, interleaved on the host -> (fnet's output, cnet's output, still
+        on ``side``)."""
+        cimg = xc
+        ff, fc = self.fnet.stage_fns(), self.cnet.stage_fns()
+        for k in range(max(len(ff), len(fc))):
+            if k < len(ff):
+                xf = ff[k](xf)
+            if k < len(fc):
+                with torch.cuda.stream(side):
+                    xc = fc[k](xc)
+        cimg.record_stream(side)  # main-stream block read on side (kept by cnet's backward)
+        return xf, xc
+
+    def _corr_block(self, fmap1, fmap2, mixed):
+        corr_dtype = torch.bfloat16 if mixed else torch.float32
+        block = AlternateCorrBlock if self.cfg.alternate_corr else CorrBlock
+        kw = {} if self.cfg.alternate_corr else dict(pyr_dtype=self.cfg.pyr_dtype)
+        return block(fmap1, fmap2, num_levels=self.cfg.corr_levels,
+                     radius=self.cfg.corr_radius, out_dtype=corr_dtype, **kw)
+
+    def _update(self, cnet, corr_fn, like, flow_init, iters, test_mode, dparams=None):
+        """The refinement loop on the context encoder's raw output ``cnet``
+        (B,hidden+context,h,w): forward's result.  ``like``: a tensor of the
+        pass's device (forward: the context encoder's input)."""
+        hdim, cdim = self.hidden_dim, self.context_dim
+        fused_train = not test_mode and FusedTrainEngine.eligible(self, like, corr_fn)
+        fused_inf = not fused_train and FusedUpdate.eligible(self, like, corr_fn)
+        if (fused_train and not self.cfg.small) or fused_inf:
+            # the fused engines split the context features and apply tanh / relu
+            # themselves, straight into their buffers (context_act)
+            net, inp = cnet, None
+        else:
+            net, inp = torch.split(cnet, [hdim, cdim], dim=1)
+            net = torch.tanh(net)
+            inp = torch.relu(inp)
+
+        coords0, coords1 = self._coords(cnet.shape[0], cnet.shape[2], cnet.shape[3], cnet.device)
+        if flow_init is not None:
+            coords1 = coords1 + flow_init
+
+        if fused_train:
+            eng = self._train_engine()
+            cstate, ctoken, otf_t = FusedTrainEngine.corr_inputs(corr_fn)
+            otf = None if not otf_t else (corr_fn.radius, corr_fn.scale, len(otf_t) - 1)
+            up = FusedTrainLoop.apply(eng, cstate, ctoken, net, inp, coords0, coords1,
+                                      iters, dparams is not None, otf, *otf_t,
+                                      *(dparams if dparams is not None else eng.params))
+            # consecutive views of one tensor: the fused loss reads it whole
+            return list(up.view(iters, *coords1.shape[:1], *up.shape[1:]).unbind(0))
+
+        eng_t = self.__dict__.get("_fused_train")
+        if (eng_t is not None and eng_t.grad_group is not None and not test_mode and self.training
+                and torch.is_grad_enabled()):
+            # DDP ignores the update-block parameters: only the fused engine reduces them
+            raise RuntimeError("data-parallel RAFT was wrapped for the fused training engine, "
+                               "but this step is not eligible for it (update-block gradients "
+                               "would not be all-reduced)")
+
+        if fused_inf:
+            eng = self._fused_engine()
+            coords1, preds, flow_up = eng.run(net, inp, corr_fn, coords0, coords1, iters, test_mode)
+            if test_mode:
+                return coords1 - coords0, flow_up
+            return preds
+
+        small = self.cfg.small
+        preds = []
+        flow_up = None
+        for itr in range(iters):
+            coords1 = coords1.detach()
+            corr = corr_fn(coords1)
+            flow = coords1 - coords0
+            last = itr == iters - 1
+            want_up = (not test_mode) or last
+            if small:
+                net, up_mask, delta_flow = self.update_block(net, inp, corr, flow)
             else:
-                net, inp = torch.split(cnet, [hdim, cdim], dim=1)
-                net = torch.tanh(net)
-                inp = torch.relu(inp)
-
-            coords0, coords1 = self.initialize_flow(cimg)
-            if flow_init is not None:
-                coords1 = coords1 + flow_init
-
-            if fused_train:
-                eng = self._train_engine()
-                cstate, ctoken, otf_t = FusedTrainEngine.corr_inputs(corr_fn)
-                otf = None if not otf_t else (corr_fn.radius, corr_fn.scale, len(otf_t) - 1)
-                up = FusedTrainLoop.apply(eng, cstate, ctoken, net, inp, coords0, coords1,
-                                          iters, dparams is not None, otf, *otf_t,
-                                          *(dparams if dparams is not None else eng.params))
-                # consecutive views of one tensor: the fused loss reads it whole
-                return list(up.view(iters, *coords1.shape[:1], *up.shape[1:]).unbind(0))
-
-            eng_t = self.__dict__.get("_fused_train")
-            if (eng_t is not None and eng_t.grad_group is not None and not test_mode and self.training
-                    and torch.is_grad_enabled()):
-                # DDP ignores the update-block parameters: only the fused engine reduces them
-                raise RuntimeError("data-parallel RAFT was wrapped for the fused training engine, "
-                                   "but this step is not eligible for it (update-block gradients "
-                                   "would not be all-reduced)")
-
-            if fused_inf:
-                eng = self._fused_engine()
-                coords1, preds, flow_up = eng.run(net, inp, corr_fn, coords0, coords1, iters, test_mode)
-                if test_mode:
-                    return coords1 - coords0, flow_up
-                return preds
-
-            small = self.cfg.small
-            preds = []
-            flow_up = None
-            for itr in range(iters):
-                coords1 = coords1.detach()
-                corr = corr_fn(coords1)
-                flow = coords1 - coords0
-                last = itr == iters - 1
-                want_up = (not test_mode) or last
-                if small:
-                    net, up_mask, delta_flow = self.update_block(net, inp, corr, flow)
-                else:
-                    net, up_mask, delta_flow = self.update_block(net, inp, corr, flow,
-                                                                 upsample=want_up)
-                coords1 = coords1 + delta_flow.float()
-                if not want_up:
-                    continue
-                if up_mask is None:
-                    flow_up = upflow8(coords1 - coords0)
-                else:
-                    flow_up = self.upsample_flow(coords1 - coords0, up_mask)
-                preds.append(flow_up)
+                net, up_mask, delta_flow = self.update_block(net, inp, corr, flow,
+                                                             upsample=want_up)
+            coords1 = coords1 + delta_flow.float()
+            if not want_up:
+                continue
+            if up_mask is None:
+                flow_up = upflow8(coords1 - coords0)
+            else:
+                flow_up = self.upsample_flow(coords1 - coords0, up_mask)
+            preds.append(flow_up)
 
         if test_mode:
             return coords1 - coords0, flow_up
         return preds
+
+    # -------------------------------------------- the two halves of an inference pass
+    def _inference_only(self, what):
+        if self.training:
+            raise ValueError(f"{what}() is an inference pass: call model.eval() first")
+        if torch.is_grad_enabled():
+            raise ValueError(f"{what}() is an inference pass: call it under torch.no_grad()")
+
+    def encode(self, image):
+        """The encoder half of an inference pass, for callers that keep a
+        frame's features (export/multiflow.py, export/pointtrack.py).  image
+        (B,3,H,W), values 0..255 -> ``(fmap, ctx)``: the feature encoder's
+        output (B,C,H/8,W/8) in the dtype the correlation block takes (bf16
+        under mixed precision on the HIP path, fp32 otherwise) and the context
+        encoder's raw (hidden + context)-channel output, before the split and
+        tanh / relu.  As in forward the feature encoder runs on the current
+        stream and the context encoder on the side stream; both outputs are
+        safe to use on the current stream."""
+        self._inference_only("encode")
+        dev = image.device
+        gpu = dev.type == "cuda"
+        xin, (x,) = self._normalise([image], gpu)
+        mixed = bool(self.cfg.mixed_precision) and gpu
+        gru_ops.begin_forward()
+        if gpu and not torch.jit.is_tracing():
+            wpack.refresh()
+        side = None
+        if gpu and self.cfg.overlap_encoders and OVERLAP["cnet"] and not torch.jit.is_tracing():
+            side = self._side_stream(dev)
+            main = torch.cuda.current_stream(dev)
+            side.wait_stream(main)
+        with self._autocast(dev):
+            if side is not None:
+                fmap, ctx = self._encode_overlapped(x, x, side)
+            else:
+                fmap = self.fnet(x)
+            if not (mixed and _ext.use_hip(fmap)):
+                fmap = fmap.float()
+            if side is not None:
+                main.wait_stream(side)
+                ctx = _StreamHandoff.apply(ctx, side)
+            else:
+                ctx = self.cnet(x)
+        return fmap, ctx
+
+    def refine(self, fmap1, fmap2, ctx, iters=12, flow_init=None):
+        """The refinement half: everything forward does after the encoders, in
+        test mode.  fmap1, fmap2 (B',C,h,w) and ctx (B',hidden+context,h,w) as
+        :meth:`encode` returns them, flow_init (B',2,h,w) or None ->
+        ``(flow_low, flow_up)`` of batch B'.  The caller assembles the batch:
+        for a bidirectional pass over K pairs, B' = 2K with the forward
+        directions first, as ``forward(..., bidirectional=True)`` orders it."""
+        self._inference_only("refine")
+        if not (fmap1.shape == fmap2.shape and fmap1.dim() == 4 and ctx.dim() == 4
+                and ctx.shape[0] == fmap1.shape[0] and ctx.shape[2:] == fmap1.shape[2:]):
+            raise ValueError(f"refine() needs fmap1, fmap2 (B,C,h,w) and ctx (B,Cc,h,w) of one batch and grid, got "
+                             f"{tuple(fmap1.shape)}, {tuple(fmap2.shape)} and {tuple(ctx.shape)}")
+        dev = ctx.device
+        mixed = bool(self.cfg.mixed_precision) and dev.type == "cuda"
+        gru_ops.begin_forward()
+        with self._autocast(dev):
+            corr_fn = self._corr_block(fmap1, fmap2, mixed)
+            return self._update(ctx, corr_fn, ctx, flow_init, iters, True)

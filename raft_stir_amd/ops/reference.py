@@ -333,3 +333,24 @@ def multi_flow_track_points(flow_fw, flow_bw, starts, start_score, start_visible
     out_err = torch.where(none, inf[0], err.gather(0, g)[0])
     choice = torch.where(none, torch.full_like(pick, -1), pick).to(torch.int32)
     return points[None], out_score[None], any_elig[None], choice[None], out_err[None], err
+
+
+def feature_ring_step(ring_f, ring_c, f_new, c_new, idx, x, ctx):
+    """The put-then-gather of csrc/feat_ring.hip, in place, from ATen index
+    ops.  ring_f (R,h,w,C), ring_c (R,h,w,Cc), f_new (1,h,w,C), c_new
+    (1,h,w,Cc); idx (K+1,) int32 on the tensors' device: K source rows, then
+    the row to write, each clamped to [0, R-1]; x (3K,h,w,C), ctx (2K,h,w,Cc):
+      ring_f[dst] = f_new, ring_c[dst] = c_new
+      x[k] = ring_f[src[k]], x[K+k] = f_new, x[2K+k] = x[k]
+      ctx[k] = ring_c[src[k]], ctx[K+k] = c_new
+    A source equal to dst sees the new features.  No host synchronisation."""
+    R, K = ring_f.shape[0], idx.shape[0] - 1
+    i = idx.long().clamp(0, R - 1)
+    src, dst = i[:K], i[K:]
+    ring_f.index_copy_(0, dst, f_new)
+    ring_c.index_copy_(0, dst, c_new)
+    x[:K] = ring_f.index_select(0, src)
+    x[K:2 * K] = f_new
+    x[2 * K:] = x[:K]
+    ctx[:K] = ring_c.index_select(0, src)
+    ctx[K:] = c_new

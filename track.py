@@ -3,7 +3,7 @@
 whole sequence, with RAFT's video warm start).
 
     python track.py --model M [--small --mixed_precision --iters 12 --no_warm_start] \
-        [--fb_check [--fb_alpha A1 A2]] [--deltas 1 4 16 inf] \
+        [--fb_check [--fb_alpha A1 A2]] [--deltas 1 4 16 inf] [--cache_features] \
         --path demo-frames --points points.txt --out tracks.csv
 
 ``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
@@ -22,6 +22,10 @@ again (``export/multiflow.py: MultiFlowTracker``): growing frame distances,
 ``frame,point,x,y,fb_err,visible,score,delta``: ``score`` the accumulated
 forward-backward error of the chain that led here (``inf`` for a lost point)
 and ``delta`` the span chosen (0: the anchor, -1: none).
+
+``--cache_features`` encodes every frame once and keeps its features on the
+device for the later steps that need them (both trackers); the columns are the
+same.
 """
 import argparse
 import csv
@@ -53,7 +57,7 @@ def _deltas(words):
 def track_multi(args, model, images, pts, dev):
     """--deltas: MultiFlowTracker and the eight-column CSV."""
     tracker = MultiFlowTracker(model, iters=args.iters, deltas=_deltas(args.deltas), fb_alpha=tuple(args.fb_alpha),
-                               warm_start=not args.no_warm_start)
+                               warm_start=not args.no_warm_start, cache_features=args.cache_features)
     padder = InputPadder(load_image(images[0], dev).shape)
     shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
     points = torch.from_numpy(pts).to(dev)[None] + shift
@@ -88,7 +92,8 @@ def track(args):
     if args.deltas:
         return track_multi(args, model, images, pts, dev)
     tracker = SequenceTracker(model, iters=args.iters, warm_start=not args.no_warm_start,
-                              fb_check=args.fb_check, fb_alpha=tuple(args.fb_alpha))
+                              fb_check=args.fb_check, fb_alpha=tuple(args.fb_alpha),
+                              cache_features=args.cache_features)
     padder = InputPadder(load_image(images[0], dev).shape)
     shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
     points = torch.from_numpy(pts).to(dev)[None] + shift
@@ -133,4 +138,6 @@ if __name__ == "__main__":
     parser.add_argument("--deltas", nargs="+", metavar="D",
                         help="track over these frame distances at once ('inf' last: the first frame as anchor) and "
                              "recover lost points: the CSV columns become x,y,fb_err,visible,score,delta")
+    parser.add_argument("--cache_features", action="store_true",
+                        help="encode every frame once and keep its features for the later steps")
     track(parser.parse_args())
