@@ -1,8 +1,8 @@
 // Device functions of the forward-backward check: the sampling rule S, the
 // inside test, the check rule and the point form built from them.  The rule
-// itself is written down in csrc/fb_check.hip; csrc/fb_check.hip and
-// csrc/multi_flow.hip both inline these functions, so their kernels cannot
-// drift apart.
+// itself is written down in csrc/fb_check.hip; csrc/fb_check.hip,
+// csrc/multi_flow.hip and csrc/dense_flow.hip all inline these functions, so
+// their kernels cannot drift apart.
 #pragma once
 
 #include "common.h"

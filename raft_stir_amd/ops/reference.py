@@ -354,3 +354,68 @@ def feature_ring_step(ring_f, ring_c, f_new, c_new, idx, x, ctx):
     x[2 * K:] = x[:K]
     ctx[:K] = ring_c.index_select(0, src)
     ctx[K:] = c_new
+
+
+def dense_multi_flow_step(flow_fw, flow_bw, ring_pos, ring_score, idx, active, alpha1: float = 0.01,
+                          alpha2: float = 0.5, track=None):
+    """The dense step of csrc/dense_flow.hip as the point form at every pixel.
+    flows (K,2,H,W); ring_pos (R,2,H,W), ring_score (R,H,W): the planar state
+    ring, changed in place; idx (K+1,) int32 on the tensors' device: K source
+    rows, then the row to write, each clamped to [0, R-1]; active (K,) bool.
+    The state of row ``src[k]`` is gathered into the (K,N,2) / (K,N) inputs of
+    :func:`multi_flow_track_points`, N = H*W, with ``start_visible =
+    start_score < +inf`` (a stored score is finite iff the pixel was visible);
+    a slot whose source is the row written counts as inactive; the score of a
+    pixel that is not visible becomes +inf; the positions and scores go to row
+    ``dst``.  -> (pos (1,2,H,W), score (1,1,H,W), visible (1,1,H,W) bool,
+    choice (1,1,H,W) int32, fb_err (1,1,H,W), cand_err (K,H,W)).  No host
+    synchronisation."""
+    K, _, H, W = flow_fw.shape
+    R, N = ring_pos.shape[0], H * W
+    i = idx.long().clamp(0, R - 1)
+    src, dst = i[:K], i[K:]
+    starts = ring_pos.index_select(0, src).reshape(K, 2, N).transpose(1, 2).contiguous()
+    start_score = ring_score.index_select(0, src).reshape(K, N)
+    inf = torch.full_like(start_score[:1], float("inf"))
+    pts, score, vis, choice, err, cand = multi_flow_track_points(
+        flow_fw, flow_bw, starts, start_score, start_score < inf, active & (src != dst), alpha1, alpha2, track=track)
+    score = torch.where(vis, score, inf)
+    pos = pts.transpose(1, 2).reshape(1, 2, H, W)
+    score = score.reshape(1, 1, H, W)
+    ring_pos.index_copy_(0, dst, pos)
+    ring_score.index_copy_(0, dst, score[0])
+    return (pos, score, vis.reshape(1, 1, H, W), choice.reshape(1, 1, H, W), err.reshape(1, 1, H, W),
+            cand.reshape(K, H, W))
+
+
+def dense_query(pos, score, points):
+    """Read a dense track field at points of the anchor frame.  pos (1,2,H,W),
+    score (1,1,H,W) (+inf: not visible), points (1,N,2) xy -> (positions
+    (1,N,2), visible (1,N) bool, score (1,N)).  For a point inside
+    [0,W-1]x[0,H-1] the position is the bilinear sample of the two planes by
+    the sampling rule S of csrc/fb_device.h (at an integer point: that pixel's
+    stored position, bit for bit), visible the AND and score the max over the
+    taps of non-zero weight.  A point outside the image or non-finite comes
+    back unchanged, not visible, with score +inf."""
+    _, _, H, W = pos.shape
+    p = points.float()
+    x, y = p[..., 0], p[..., 1]
+    inside = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)  # NaN fails
+    zero = torch.zeros_like(x)
+    xs, ys = torch.where(inside, x, zero), torch.where(inside, y, zero)
+    u, v = _fb_sample(pos.float(), xs, ys, torch.float32)
+    out = torch.where(inside[..., None], torch.stack([u, v], dim=-1), p)
+    x0, y0 = torch.floor(xs), torch.floor(ys)
+    wx, wy = xs - x0, ys - y0
+    ux, uy = 1 - wx, 1 - wy
+    xi0, yi0 = x0.long(), y0.long()
+    flat = score.float().reshape(1, H * W)
+    worst = torch.full_like(x, float("-inf"))
+    for dx, dy, w in ((0, 0, ux * uy), (1, 0, wx * uy), (0, 1, ux * wy), (1, 1, wx * wy)):
+        xi, yi = xi0 + dx, yi0 + dy
+        use = (w != 0) & (xi < W) & (yi < H)
+        val = flat.gather(1, yi.clamp(0, H - 1) * W + xi.clamp(0, W - 1))
+        worst = torch.where(use, torch.maximum(worst, val), worst)
+    inf = torch.full_like(x, float("inf"))
+    worst = torch.where(inside, worst, inf)
+    return out, worst < inf, worst

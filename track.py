@@ -5,6 +5,7 @@ whole sequence, with RAFT's video warm start).
     python track.py --model M [--small --mixed_precision --iters 12 --no_warm_start] \
         [--fb_check [--fb_alpha A1 A2]] [--deltas 1 4 16 inf] [--cache_features] \
         --path demo-frames --points points.txt --out tracks.csv
+    python track.py --model M --dense --deltas 1 4 16 inf [--points points.txt] --path demo-frames --out tracks/
 
 ``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
 CSV has a ``frame,point,x,y`` row for every point in every frame (frame 0 holds
@@ -26,6 +27,16 @@ and ``delta`` the span chosen (0: the anchor, -1: none).
 ``--cache_features`` encodes every frame once and keeps its features on the
 device for the later steps that need them (both trackers); the columns are the
 same.
+
+``--dense`` (with ``--deltas``) tracks every pixel of the first frame
+(``export/denseflow.py: DenseMultiFlowTracker``) and needs no ``--points``;
+``--out`` then names a directory, which receives per frame t the long-term flow
+``0 -> t`` as ``flow_TTTT.flo`` and the visibility as the 8-bit image
+``visible_TTTT.png`` (255: visible), both cropped back from the padding, with
+the flow between unpadded coordinates.  ``--dense`` with ``--points`` writes the
+eight-column CSV ``tracks.csv`` into that directory as well, the points read
+from the dense field after every step (``DenseMultiFlowTracker.query``);
+``fb_err`` and ``delta`` are then those of the pixel nearest to the point.
 """
 import argparse
 import csv
@@ -39,6 +50,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from raft_stir_amd.cli_common import add_model_args, default_device, load_image, load_model  # noqa: E402
+from raft_stir_amd.data.frame_utils import writeFlow  # noqa: E402
+from raft_stir_amd.export.denseflow import DenseMultiFlowTracker  # noqa: E402
 from raft_stir_amd.export.multiflow import MultiFlowTracker  # noqa: E402
 from raft_stir_amd.export.pointtrack import SequenceTracker  # noqa: E402
 from raft_stir_amd.utils.padder import InputPadder  # noqa: E402
@@ -69,14 +82,53 @@ def track_multi(args, model, images, pts, dev):
     traj, err, vis, score, delta = (torch.cat(c) for c in cols)
     traj = (traj - shift).cpu().numpy()
     err, vis, score, delta = (v.cpu().numpy() for v in (err, vis, score, delta))
-    with open(args.out, "w", newline="") as f:
+    _write_csv(args.out, traj, err, vis, score, delta)
+    print(f"wrote {traj.shape[0]} frames x {traj.shape[1]} points to {args.out}")
+    return traj
+
+
+def _write_csv(path, traj, err, vis, score, delta):
+    with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["frame", "point", "x", "y", "fb_err", "visible", "score", "delta"])
         for t in range(traj.shape[0]):
             for n in range(traj.shape[1]):
                 w.writerow([t, n, f"{traj[t, n, 0]:.4f}", f"{traj[t, n, 1]:.4f}", f"{err[t, n]:.4f}", int(vis[t, n]),
                             f"{score[t, n]:.4f}", int(delta[t, n])])
-    print(f"wrote {traj.shape[0]} frames x {traj.shape[1]} points to {args.out}")
+
+
+def track_dense(args, model, images, pts, dev):
+    """--dense: DenseMultiFlowTracker; a .flo and a visibility image per frame
+    in the directory --out, and with --points the eight-column CSV from query()."""
+    from PIL import Image
+    tracker = DenseMultiFlowTracker(model, iters=args.iters, deltas=_deltas(args.deltas), fb_alpha=tuple(args.fb_alpha),
+                                    warm_start=not args.no_warm_start, cache_features=args.cache_features)
+    os.makedirs(args.out, exist_ok=True)
+    padder = InputPadder(load_image(images[0], dev).shape)
+    shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
+    points = None if pts is None else torch.from_numpy(pts).to(dev)[None] + shift
+    cols = [[], [], [], [], []]
+    for t, f in enumerate(images):
+        tracker.step(padder.pad(load_image(f, dev))[0])
+        # a difference of two positions: the padding's shift cancels
+        flow = padder.unpad(tracker.flow)[0].permute(1, 2, 0).cpu().numpy()
+        vis = padder.unpad(tracker.visible)[0, 0].cpu().numpy()
+        writeFlow(os.path.join(args.out, f"flow_{t:04d}.flo"), flow)
+        Image.fromarray(vis.astype(np.uint8) * 255).save(os.path.join(args.out, f"visible_{t:04d}.png"))
+        if points is not None:
+            p, v, s = tracker.query(points)
+            H, W = tracker.pos.shape[-2:]
+            near = points[0].round().long()
+            near = (near[:, 1].clamp(0, H - 1) * W + near[:, 0].clamp(0, W - 1))[None]
+            for c, x in zip(cols, (p - shift, tracker.fb_err.view(1, -1).gather(1, near), v, s,
+                                   tracker.delta.view(1, -1).gather(1, near))):
+                c.append(x)
+    print(f"wrote {len(images)} flow fields and visibility maps to {args.out}")
+    if points is None:
+        return None
+    traj, err, vis, score, delta = (torch.cat(c).cpu().numpy() for c in cols)
+    _write_csv(os.path.join(args.out, "tracks.csv"), traj, err, vis, score, delta)
+    print(f"wrote {traj.shape[0]} frames x {traj.shape[1]} points to {os.path.join(args.out, 'tracks.csv')}")
     return traj
 
 
@@ -86,9 +138,13 @@ def track(args):
     images = sorted(glob.glob(os.path.join(args.path, "*.png")) + glob.glob(os.path.join(args.path, "*.jpg")))
     if len(images) < 2:
         raise FileNotFoundError(f"at least two frames (*.png, *.jpg) expected in {args.path!r}")
-    pts = np.loadtxt(args.points, dtype=np.float32, ndmin=2)
-    if pts.shape[1] != 2:
-        raise ValueError(f"{args.points}: one 'x y' per line expected")
+    pts = None
+    if args.points:
+        pts = np.loadtxt(args.points, dtype=np.float32, ndmin=2)
+        if pts.shape[1] != 2:
+            raise ValueError(f"{args.points}: one 'x y' per line expected")
+    if args.dense:
+        return track_dense(args, model, images, pts, dev)
     if args.deltas:
         return track_multi(args, model, images, pts, dev)
     tracker = SequenceTracker(model, iters=args.iters, warm_start=not args.no_warm_start,
@@ -120,13 +176,13 @@ def track(args):
     return traj
 
 
-if __name__ == "__main__":
+def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     add_model_args(parser)
     parser.add_argument("--model", help="restore checkpoint")
     parser.add_argument("--path", default="demo-frames", help="folder of frames")
-    parser.add_argument("--points", required=True, help="text file, one 'x y' per line")
-    parser.add_argument("--out", default="tracks.csv")
+    parser.add_argument("--points", help="text file, one 'x y' per line (required unless --dense)")
+    parser.add_argument("--out", default="tracks.csv", help="the CSV to write; with --dense a directory")
     parser.add_argument("--small", action="store_true", help="use small model")
     parser.add_argument("--mixed_precision", action="store_true", help="use mixed precision")
     parser.add_argument("--iters", type=int, default=12)
@@ -140,4 +196,16 @@ if __name__ == "__main__":
                              "recover lost points: the CSV columns become x,y,fb_err,visible,score,delta")
     parser.add_argument("--cache_features", action="store_true",
                         help="encode every frame once and keep its features for the later steps")
-    track(parser.parse_args())
+    parser.add_argument("--dense", action="store_true",
+                        help="with --deltas: track every pixel of the first frame and write a .flo and a visibility "
+                             "image per frame into the directory --out (with --points: tracks.csv there too)")
+    args = parser.parse_args(argv)
+    if args.dense and not args.deltas:
+        parser.error("--dense needs --deltas")
+    if not args.dense and not args.points:
+        parser.error("the following arguments are required: --points")
+    return args
+
+
+if __name__ == "__main__":
+    track(parse_args())
