@@ -14,7 +14,8 @@ from __future__ import annotations
 import torch
 
 from ..ops.multi_flow import MAX_SLOTS
-from .pointtrack import NUMITERS
+from .pointtrack import (NUMITERS, check_step_inputs, check_tracker_options, encode_and_gather, encode_first,
+                         image_buffer)
 
 
 def _check_deltas(deltas):
@@ -36,9 +37,10 @@ def _check_deltas(deltas):
 
 
 def ring_index_table(deltas):
-    """The feature ring's index rows of a ``cache_features`` tracker, one per
-    step: ``[src_0 .. src_{K-1}, dst]``, the ring row each slot reads and the
-    row the new frame is written to (ops.feature_ring_step).  The ring has
+    """The index rows of the tracker's rings (of frames, or of features with
+    ``cache_features``, and of what was returned for them), one per step:
+    ``[src_0 .. src_{K-1}, dst]``, the ring row each slot reads and the row
+    the new frame is written to (ops.feature_ring_step).  A ring has
     L + 2 rows, L the longest finite span: frame t lives in row t % (L + 1)
     and row L + 1 keeps the anchor frame.  An active slot of span D reads
     frame t - D, an inactive one frame 0 (row 0, not yet overwritten: t < L),
@@ -103,12 +105,20 @@ class MultiFlowTracker:
     starts from zeros.
 
     On the GPU all of this is one captured hipGraph per (frame shape, N,
-    deltas) over static buffers.  The frames of the last max(D) steps and what
-    was returned for them stay on the device; before a replay the host issues
-    only device-to-device copies chosen by indices it knows from t, so with
-    frames and points on the device a step does not synchronise with the
-    host, and a frame is uploaded once.  On a CPU model the same loop runs
-    eagerly on the ATen oracle.
+    deltas) over static buffers.  The last L + 1 frames (L the longest finite
+    span) stay on the device in a ring of L + 2 rows, and what was returned
+    for them and for the anchor in rings ``hist_p`` / ``hist_s`` / ``hist_v``
+    of the same row layout (:func:`ring_index_table`).  The graph gathers the
+    starts from the rows ``idx[:K]`` and stores the new result in row
+    ``idx[K]``.  Before a replay the host issues the frame upload, one row of
+    the index table into ``idx``, the ``active`` row when it changes, the
+    init and one image copy per finite slot from the frame ring into ``i1``,
+    and after it one of the new frame into the ring, the rows taken from the
+    same table row (the anchor's image stays in ``i1``).  No state is copied
+    per slot, and with frames and points on the device a step does not
+    synchronise with the host; a frame is uploaded once.  The first frame of
+    a sequence is stored by a small graph of its own.  On a CPU model the
+    same step runs eagerly on the ATen oracle.
 
     ``cache_features=True`` encodes every frame once.  The step above runs
     both encoders on 2K images, K of them the new frame and the others frames
@@ -120,15 +130,15 @@ class MultiFlowTracker:
         ops.feature_ring_step(ring_f, ring_c, f, c, idx, x, ctx) # store, and gather the 2K pairs
         lo, up = model.refine(x[:2K], x[K:], ctx, iters, flow_init=init)
 
-    followed by the same selection and warm start; what was returned for the
-    stored frames lives in rings of the same row layout and is read and
-    written inside the graph with the same ``idx`` (:func:`ring_index_table`).
-    Before a replay the host issues the frame upload, one row of the index
-    table, the ``active`` row when it changes and the init: no per-slot
-    copies.  The first frame of a sequence is encoded by a small graph of its
-    own.  The flows differ from the uncached tracker's only by the batch size
-    at which the encoders ran.
+    followed by the same selection and warm start.  The feature ring takes
+    the frame ring's place, with the same rows, read and written inside the
+    graph by the same ``idx``, so the host issues none of the image copies;
+    the rest of the step is unchanged, and the small graph of the first
+    frame encodes it.  The flows differ from the uncached tracker's only by
+    the batch size at which the encoders ran.
     """
+
+    _needs_points = True  # the first frame comes with the points to follow
 
     def __init__(self, model, iters: int = NUMITERS, deltas=(1, 2, 4, 8, None), fb_alpha=(0.01, 0.5),
                  warm_start: bool = True, cache_features: bool = False):
@@ -136,15 +146,10 @@ class MultiFlowTracker:
         self.iters = iters
         self.deltas = _check_deltas(deltas)
         self.K = len(self.deltas)
-        self._finite = [d for d in self.deltas if d is not None]
-        self.L = max(self._finite, default=1)  # frames kept
-        self.fb_alpha = (float(fb_alpha[0]), float(fb_alpha[1]))
-        if not (self.fb_alpha[0] >= 0 and self.fb_alpha[1] >= 0):
-            raise ValueError(f"fb_alpha must be two numbers >= 0, got {fb_alpha}")
+        self.L = max((d for d in self.deltas if d is not None), default=1)  # frames kept
+        self._table = ring_index_table(self.deltas)
+        self.fb_alpha, self.cache_features = check_tracker_options(model, fb_alpha, cache_features)
         self.warm_start = warm_start
-        self.cache_features = bool(cache_features)
-        if self.cache_features and not (hasattr(model, "encode") and hasattr(model, "refine")):
-            raise ValueError("cache_features=True needs a model with encode() and refine()")
         self.graphs = {}
         self._wkey = None
         self.reset()
@@ -153,7 +158,6 @@ class MultiFlowTracker:
         """Forget the frames, the points and the inits."""
         self.t = 0
         self._st = None       # the buffers of the running sequence
-        self._hist = None     # what was returned for the last L frames, by frame index mod L
         self._active_row = None
         self._next = None     # the init of the next step, (2K,2,h,w)
         self._shape = None
@@ -164,32 +168,16 @@ class MultiFlowTracker:
     # ------------------------------------------------------------------ public
     @torch.no_grad()
     def step(self, frame, points=None):
-        if frame.dim() != 4 or frame.shape[0] != 1 or frame.shape[1] != 3:
-            raise ValueError(f"frame must be (1,3,H,W), got {tuple(frame.shape)}")
-        if frame.shape[-2] % 8 or frame.shape[-1] % 8:
-            raise ValueError(f"frame height and width must be multiples of 8, got {tuple(frame.shape[-2:])}")
-        if self._shape is not None and self._shape != tuple(frame.shape):
-            raise ValueError(f"frame shape changed within a sequence: {self._shape} -> "
-                             f"{tuple(frame.shape)} (call reset())")
-        if self.t == 0:
-            if points is None:
-                raise ValueError("the first step of a sequence needs points")
-            if points.dim() != 3 or points.shape[0] != 1 or points.shape[2] != 2:
-                raise ValueError(f"points must be (1,N,2), got {tuple(points.shape)}")
-        elif points is not None:
+        from ..runtime.weights import refresh_if_moved
+        check_step_inputs(frame, self._shape, points if self.t == 0 else None)
+        if self.t == 0 and points is None and self._needs_points:
+            raise ValueError("the first step of a sequence needs points")
+        if self.t > 0 and points is not None:
             raise ValueError("points are given with the first frame of a sequence only (call reset())")
         dev = next(self.model.parameters()).device
         if dev.type == "cuda":
-            from ..runtime.weights import refresh_all, weights_key
-            wkey = weights_key(self.model)
-            if self._wkey is not None and wkey != self._wkey:
-                refresh_all(self.model)  # weights moved since capture: re-pack into the captured storage
-            self._wkey = wkey
-        if self.cache_features:
-            return self._first_cached(dev, frame, points) if self.t == 0 else self._advance_cached(frame)
-        if self.t == 0:
-            return self._first(dev, frame, points)
-        return self._advance(frame)
+            self._wkey = refresh_if_moved(self.model, self._wkey)
+        return self._first(dev, frame, points) if self.t == 0 else self._advance(frame)
 
     @torch.no_grad()
     def track(self, frames, points):
@@ -208,123 +196,150 @@ class MultiFlowTracker:
         return torch.stack(traj), torch.stack(vis), torch.stack(score), torch.stack(delta)
 
     # ------------------------------------------------------------------- state
-    def _buffers(self, dev, frame, N):
-        """The static inputs of a step, the frame ring and the constants."""
+    def _buffers(self, dev, frame, points):
+        """The static inputs of a step, the rings and the constants.  Every
+        ring has L + 2 rows in the layout of :func:`ring_index_table` (the
+        frame ring leaves the anchor's row unused: its image stays in ``i1``);
+        the feature ring of a ``cache_features`` tracker comes with the first frame."""
         K, L = self.K, self.L
         H, W = frame.shape[-2:]
-        fmt = torch.channels_last if dev.type == "cuda" else torch.contiguous_format
-        return {
-            "i1": torch.zeros(K, 3, H, W, device=dev).contiguous(memory_format=fmt),
-            "starts": torch.zeros(K, N, 2, device=dev),
-            "sscore": torch.zeros(K, N, device=dev),
-            "svis": torch.ones(K, N, dtype=torch.bool, device=dev),
-            "ring": torch.zeros(L, 3, H, W, device=dev).contiguous(memory_format=fmt),
-            **self._common(dev, frame, N),
-        }
-
-    def _common(self, dev, frame, N):
-        """What the uncached and the cached step share: the new frame, the
-        active slots, the init and the constants."""
-        K, L = self.K, self.L
-        H, W = frame.shape[-2:]
-        fmt = torch.channels_last if dev.type == "cuda" else torch.contiguous_format
         span = [float(d) if d is not None else 1.0 for d in self.deltas]
-        table = [[(d is not None and t >= d) or (d is None and t >= 1) for d in self.deltas] for t in range(L + 1)]
-        return {
-            "frame": torch.zeros(1, 3, H, W, device=dev).contiguous(memory_format=fmt),
+        active = [[(d is not None and t >= d) or (d is None and t >= 1) for d in self.deltas] for t in range(L + 1)]
+        table = self._table
+        st = {
+            "frame": image_buffer((1, 3, H, W), dev),
             "active": torch.ones(K, dtype=torch.bool, device=dev),
             "init": torch.zeros(2 * K, 2, H // 8, W // 8, device=dev),
             "zero": torch.zeros(2 * K, 2, H // 8, W // 8, device=dev),
+            "idx_table": torch.tensor(table, dtype=torch.int32, device=dev),
+            "idx": torch.tensor(table[0], dtype=torch.int32, device=dev),
             # constants: g*D per field, the anchor's fields, D per slot, the active slots at t = 0..L
             "scale": torch.tensor(span + [-s for s in span], device=dev).view(2 * K, 1, 1, 1),
             "anchor": torch.tensor([d is None for d in self.deltas] * 2, device=dev).view(2 * K, 1, 1, 1),
             "delta": torch.tensor([d or 0 for d in self.deltas], dtype=torch.int32, device=dev),
-            "table": torch.tensor(table, dtype=torch.bool, device=dev),
-            "inf": torch.full((1, N), float("inf"), device=dev),
-            "minus": torch.full((1, N), -1, dtype=torch.int32, device=dev),
-            "graph": None,
+            "table": torch.tensor(active, dtype=torch.bool, device=dev),
+            "graph0": None, "graph": None,
+            **self._history(dev, frame, points),
         }
+        if not self.cache_features:
+            st["ring"], st["i1"] = image_buffer((L + 2, 3, H, W), dev), image_buffer((K, 3, H, W), dev)
+        return st
+
+    def _history(self, dev, frame, points):
+        """What was returned for the frame of every ring row, and the constants of its shape."""
+        R, N = self.L + 2, points.shape[1]
+        return {"hist_p": torch.zeros(R, N, 2, device=dev), "hist_s": torch.zeros(R, N, device=dev),
+                "hist_v": torch.ones(R, N, dtype=torch.bool, device=dev),
+                "inf": torch.full((1, N), float("inf"), device=dev),
+                "minus": torch.full((1, N), -1, dtype=torch.int32, device=dev)}
+
+    def _run_first(self, st):
+        """The first frame of a sequence: its features into ring row 0, which
+        the inactive slots read too, and into the anchor's row; without
+        ``cache_features`` the frame into row 0 and into every slot of ``i1``,
+        where the anchor slot's stays for the whole sequence."""
+        if self.cache_features:
+            encode_first(self.model, st, self.L + 2, (0, self.L + 1), self.K)
+        else:
+            st["ring"][0].copy_(st["frame"][0])
+            st["i1"].copy_(st["frame"].expand(self.K, -1, -1, -1))
+
+    def _flows(self, st):
+        """(lo, up) of the K pairs in both directions: the only place in the
+        graph where the step of a ``cache_features`` tracker differs."""
+        K = self.K
+        if self.cache_features:
+            x, ctx = encode_and_gather(self.model, st)
+            return self.model.refine(x[:2 * K], x[K:], ctx, iters=self.iters, flow_init=st["init"])
+        return self.model(st["i1"], st["frame"].expand(K, -1, -1, -1), iters=self.iters, flow_init=st["init"],
+                          test_mode=True, bidirectional=True)
 
     def _run(self, st):
         """One step on the static inputs: (lo, up, points, score, visible,
         delta, fb_err, cand_err, next init)."""
-        K = self.K
-        lo, up = self.model(st["i1"], st["frame"].expand(K, -1, -1, -1), iters=self.iters, flow_init=st["init"],
-                            test_mode=True, bidirectional=True)
-        return self._select(st, lo, up, st["starts"], st["sscore"], st["svis"])
-
-    def _select(self, st, lo, up, starts, sscore, svis):
-        """The points' choice among the K flow pairs and the next init."""
-        from ..ops import forward_interpolate, multi_flow_track_points
-        K = self.K
-        pts, score, vis, choice, err, cand = multi_flow_track_points(
-            up[:K], up[K:], starts, sscore, svis, st["active"], *self.fb_alpha)
-        score = torch.where(vis, score, st["inf"])  # a lost point: nothing chains from it with a finite score
+        lo, up = self._flows(st)
+        pts, score, vis, choice, err, cand = self._choose(st, up)
         span = st["delta"].index_select(0, choice.clamp(min=0).view(-1).long()).view(choice.shape)
         delta = torch.where(choice >= 0, span, st["minus"])
-        nxt = None
-        if self.warm_start:
-            lo32 = lo.float()
-            nxt = st["scale"] * forward_interpolate(lo32 / st["scale"])
-            nxt = torch.where(st["anchor"], lo32, nxt)
-            # a slot that is inactive now starts its first active step from zeros
-            nxt = torch.where(torch.cat([st["active"], st["active"]]).view(2 * K, 1, 1, 1), nxt, st["zero"])
-        return lo, up, pts, score, vis, delta, err, cand, nxt
+        return lo, up, pts, score, vis, delta, err, cand, self._next_init(st, lo)
 
-    def _capture(self, dev, st, frame, points):
-        st["i1"].copy_(frame.expand(self.K, -1, -1, -1))
-        st["frame"].copy_(frame)
-        st["starts"].copy_(points.expand(self.K, -1, -1))
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._run(st)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            st["out"] = self._run(st)
-        st["graph"] = g
+    def _choose(self, st, up):
+        """The points' choice among the K flow pairs, from and into the history rings."""
+        from ..ops import multi_flow_track_points
+        K = self.K
+        src, dst = st["idx"][:K], st["idx"][K:].long()
+        pts, score, vis, choice, err, cand = multi_flow_track_points(
+            up[:K], up[K:], st["hist_p"].index_select(0, src), st["hist_s"].index_select(0, src),
+            st["hist_v"].index_select(0, src), st["active"], *self.fb_alpha)
+        score = torch.where(vis, score, st["inf"])  # a lost point: nothing chains from it with a finite score
+        st["hist_p"].index_copy_(0, dst, pts)
+        st["hist_s"].index_copy_(0, dst, score)
+        st["hist_v"].index_copy_(0, dst, vis)
+        return pts, score, vis, choice, err, cand
+
+    def _next_init(self, st, lo):
+        """The warm start of the next step from this step's ``lo`` (None without)."""
+        from ..ops import forward_interpolate
+        if not self.warm_start:
+            return None
+        lo32 = lo.float()
+        nxt = st["scale"] * forward_interpolate(lo32 / st["scale"])
+        nxt = torch.where(st["anchor"], lo32, nxt)
+        # a slot that is inactive now starts its first active step from zeros
+        return torch.where(torch.cat([st["active"], st["active"]]).view(2 * self.K, 1, 1, 1), nxt, st["zero"])
 
     def _first(self, dev, frame, points):
-        N = points.shape[1]
-        key = (tuple(frame.shape), N, self.deltas)
+        shape = tuple(frame.shape)
+        key = ((shape,) + (() if points is None else (points.shape[1],)) + (self.deltas,)
+               + (("cache_features",) if self.cache_features else ()))
         st = self.graphs.get(key)
-        if st is None:
-            st = self.graphs[key] = self._buffers(dev, frame, N)
-            if dev.type == "cuda":
-                self._capture(dev, st, frame, points)
-        self._st, self._shape = st, tuple(frame.shape)
-        p = points.to(dev, torch.float32).clone()
+        new = st is None
+        if new:
+            st = self.graphs[key] = self._buffers(dev, frame, points)
         st["frame"].copy_(frame)
-        st["ring"][0].copy_(st["frame"][0])
-        self.points = p
+        if st["graph0"] is not None:
+            st["graph0"].replay()
+        else:
+            self._run_first(st)
+        if new and dev.type == "cuda":
+            # on the first step's inputs: the warm-up runs write the ring rows that the first step writes
+            from ..runtime.graph import capture
+            st["graph0"], _ = capture(dev, lambda: self._run_first(st))
+            st["graph"], st["out"] = capture(dev, lambda: self._run(st))
+        self._st, self._shape = st, shape
+        self._next = st["zero"]
+        self.next_init = self._next
+        self.t = 1
+        return self._start(st, dev, frame, points)
+
+    def _start(self, st, dev, frame, points):
+        """The state of a sequence's first frame: the points, score 0, visible,
+        in row 0 (which the inactive slots name too) and in the anchor's row."""
+        N = points.shape[1]
+        self.points = points.to(dev, torch.float32).clone()
         self.visible = torch.ones(1, N, dtype=torch.bool, device=dev)
         self.score = torch.zeros(1, N, device=dev)
         self.fb_err = torch.zeros(1, N, device=dev)
         self.delta = torch.zeros(1, N, dtype=torch.int32, device=dev)
-        self._hist = [None] * self.L
-        self._hist[0] = (self.points, self.score, self.visible)
-        if self.deltas[-1] is None:  # the anchor slot's inputs do not change within a sequence
-            k = self.K - 1
-            st["i1"][k].copy_(st["frame"][0])
-            st["starts"][k].copy_(p[0])
-            st["sscore"][k].zero_()
-            st["svis"][k].fill_(True)
-        self._next = st["zero"]
-        self.next_init = self._next
-        self.t = 1
+        for row in (0, self.L + 1):
+            st["hist_p"][row].copy_(self.points[0])
+            st["hist_s"][row].zero_()
+            st["hist_v"][row].fill_(True)
         return self.points
 
     def _advance(self, frame):
+        """Before the replay the host issues the frame upload, one row of the
+        index table, the ``active`` row when it changes and the init; without
+        ``cache_features`` also one image copy per finite slot and one after
+        the replay, by the same row of the table.  The ring row written is
+        never among the rows read (D <= L, :func:`ring_index_table`)."""
         st, t, L = self._st, self.t, self.L
-        for k, d in enumerate(self._finite):
-            src = (t - d if t >= d else 0) % L  # inactive: the oldest stored frame, frame 0
-            p, s, v = self._hist[src]
-            st["i1"][k].copy_(st["ring"][src])
-            st["starts"][k].copy_(p[0])
-            st["sscore"][k].copy_(s[0])
-            st["svis"][k].copy_(v[0])
+        step = ring_index_row(t, L)
+        st["idx"].copy_(st["idx_table"][step])
+        if not self.cache_features:
+            for k, d in enumerate(self.deltas):
+                if d is not None:
+                    st["i1"][k].copy_(st["ring"][self._table[step][k]])
         row = min(t, L)
         if row != self._active_row:
             st["active"].copy_(st["table"][row])
@@ -336,138 +351,19 @@ class MultiFlowTracker:
             out = st["out"]
         else:
             out = self._run(st)
-        st["ring"][t % L].copy_(st["frame"][0])
-        self._publish(st, out)
-        self._hist[t % L] = (self.points, self.score, self.visible)
-        return self.points
-
-    def _publish(self, st, out):
-        """The attributes of a step from the graph's outputs; the step is counted."""
-        lo, up, pts, score, vis, delta, err, cand, nxt = out
-        self.points, self.score, self.visible = pts.clone(), score.clone(), vis.clone()
-        self.delta, self.fb_err, self.cand_err = delta.clone(), err.clone(), cand
+        if not self.cache_features:
+            st["ring"][self._table[step][-1]].copy_(st["frame"][0])
+        lo, up, nxt = out[0], out[1], out[8]
         K = self.K
         self.flow_low, self.flow_bw_low, self.flow_up, self.flow_bw_up = lo[:K], lo[K:], up[:K], up[K:]
         self._next = nxt if self.warm_start else st["zero"]
         self.flow_init, self.next_init = st["init"], self._next
         self.t += 1
+        return self._publish(*out[2:8])
 
-    # ---------------------------------------------------------- cache_features
-    def _buffers_cached(self, dev, frame, N):
-        """The static buffers of the cached step: :meth:`_common`, the feature
-        and history rings and the index table.
-        The features' shapes and dtype come from encoding ``frame``, eagerly;
-        the rings are left holding it as a sequence's first frame."""
-        from ..ops import to_nhwc
-        K, R = self.K, self.L + 2
-        st = self._common(dev, frame, N)
-        st["frame"].copy_(frame)
-        f, c = self.model.encode(st["frame"])
-        f, c = to_nhwc(f), to_nhwc(c)
-        if f.dtype != c.dtype:
-            raise ValueError(f"cache_features: encode() returned {f.dtype} features and {c.dtype} context")
-        st.update({
-            "ring_f": f.new_zeros((R,) + tuple(f.shape[1:])), "ring_c": c.new_zeros((R,) + tuple(c.shape[1:])),
-            "x": f.new_zeros((3 * K,) + tuple(f.shape[1:])), "ctx": c.new_zeros((2 * K,) + tuple(c.shape[1:])),
-            # what was returned for the frame of every ring row
-            "hist_p": torch.zeros(R, N, 2, device=dev), "hist_s": torch.zeros(R, N, device=dev),
-            "hist_v": torch.ones(R, N, dtype=torch.bool, device=dev),
-            "idx_table": torch.tensor(ring_index_table(self.deltas), dtype=torch.int32, device=dev),
-            "idx": torch.zeros(K + 1, dtype=torch.int32, device=dev),
-            "graph0": None,
-        })
-        st["idx"].copy_(st["idx_table"][0])
-        self._store_first(st, f, c)
-        return st
-
-    def _run_first(self, st):
-        """The first frame of a sequence: encoded into row 0 and the anchor's row."""
-        from ..ops import to_nhwc
-        f, c = self.model.encode(st["frame"])
-        self._store_first(st, to_nhwc(f), to_nhwc(c))
-
-    def _store_first(self, st, f, c):
-        for row in (0, self.L + 1):
-            st["ring_f"][row].copy_(f[0])
-            st["ring_c"][row].copy_(c[0])
-
-    def _run_cached(self, st):
-        """One step on the static inputs, as :meth:`_run`."""
-        from ..ops import feature_ring_step, from_nhwc, to_nhwc
-        K = self.K
-        f, c = self.model.encode(st["frame"])
-        feature_ring_step(st["ring_f"], st["ring_c"], to_nhwc(f), to_nhwc(c), st["idx"], st["x"], st["ctx"])
-        x = from_nhwc(st["x"])
-        lo, up = self.model.refine(x[:2 * K], x[K:], from_nhwc(st["ctx"]), iters=self.iters, flow_init=st["init"])
-        idx = st["idx"].long()
-        src, dst = idx[:K], idx[K:]
-        out = self._select(st, lo, up, st["hist_p"].index_select(0, src), st["hist_s"].index_select(0, src),
-                           st["hist_v"].index_select(0, src))
-        st["hist_p"].index_copy_(0, dst, out[2])
-        st["hist_s"].index_copy_(0, dst, out[3])
-        st["hist_v"].index_copy_(0, dst, out[4])
-        return out
-
-    def _capture_cached(self, dev, st):
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._run_first(st)
-                self._run_cached(st)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        g0 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g0):
-            self._run_first(st)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            st["out"] = self._run_cached(st)
-        st["graph0"], st["graph"] = g0, g
-
-    def _first_cached(self, dev, frame, points):
-        N = points.shape[1]
-        key = (tuple(frame.shape), N, self.deltas, "cache_features")
-        st = self.graphs.get(key)
-        if st is None:
-            st = self.graphs[key] = self._buffers_cached(dev, frame, N)  # encodes this frame into the rings
-            if dev.type == "cuda":
-                self._capture_cached(dev, st)
-        else:
-            st["frame"].copy_(frame)
-            if st["graph0"] is not None:
-                st["graph0"].replay()
-            else:
-                self._run_first(st)
-        self._st, self._shape = st, tuple(frame.shape)
-        p = points.to(dev, torch.float32).clone()
-        self.points = p
-        self.visible = torch.ones(1, N, dtype=torch.bool, device=dev)
-        self.score = torch.zeros(1, N, device=dev)
-        self.fb_err = torch.zeros(1, N, device=dev)
-        self.delta = torch.zeros(1, N, dtype=torch.int32, device=dev)
-        # frame 0's row, which the inactive slots read too, and the anchor's
-        for row in (0, self.L + 1):
-            st["hist_p"][row].copy_(p[0])
-            st["hist_s"][row].zero_()
-            st["hist_v"][row].fill_(True)
-        self._next = st["zero"]
-        self.next_init = self._next
-        self.t = 1
-        return self.points
-
-    def _advance_cached(self, frame):
-        st, t, L = self._st, self.t, self.L
-        st["idx"].copy_(st["idx_table"][ring_index_row(t, L)])
-        row = min(t, L)
-        if row != self._active_row:
-            st["active"].copy_(st["table"][row])
-            self._active_row = row
-        st["frame"].copy_(frame)
-        st["init"].copy_(self._next)
-        if st["graph"] is not None:
-            st["graph"].replay()
-            out = st["out"]
-        else:
-            out = self._run_cached(st)
-        self._publish(st, out)
+    def _publish(self, pts, score, vis, delta, err, cand):
+        """The attributes that describe the returned positions: tensors of the
+        caller's own (the history rings keep theirs)."""
+        self.points, self.score, self.visible = pts.clone(), score.clone(), vis.clone()
+        self.delta, self.fb_err, self.cand_err = delta.clone(), err.clone(), cand
         return self.points

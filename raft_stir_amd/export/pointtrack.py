@@ -145,6 +145,65 @@ def export_pointtrack(model, path_prefix="raft_pointtrackSTIR", size=(512, 640),
     return out
 
 
+def check_step_inputs(frame, seq_shape, points):
+    """What every tracker's ``step`` asks of its inputs.  ``seq_shape``: the
+    frame shape of the running sequence, None before its first frame;
+    ``points`` may be None."""
+    if frame.dim() != 4 or frame.shape[0] != 1 or frame.shape[1] != 3:
+        raise ValueError(f"frame must be (1,3,H,W), got {tuple(frame.shape)}")
+    if frame.shape[-2] % 8 or frame.shape[-1] % 8:
+        raise ValueError(f"frame height and width must be multiples of 8, got {tuple(frame.shape[-2:])}")
+    if seq_shape is not None and seq_shape != tuple(frame.shape):
+        raise ValueError(f"frame shape changed within a sequence: {seq_shape} -> "
+                         f"{tuple(frame.shape)} (call reset())")
+    if points is not None and (points.dim() != 3 or points.shape[0] != 1 or points.shape[2] != 2):
+        raise ValueError(f"points must be (1,N,2), got {tuple(points.shape)}")
+
+
+def check_tracker_options(model, fb_alpha, cache_features):
+    """-> (fb_alpha as two floats, cache_features as a bool), both checked."""
+    alpha = (float(fb_alpha[0]), float(fb_alpha[1]))
+    if not (alpha[0] >= 0 and alpha[1] >= 0):
+        raise ValueError(f"fb_alpha must be two numbers >= 0, got {fb_alpha}")
+    if cache_features and not (hasattr(model, "encode") and hasattr(model, "refine")):
+        raise ValueError("cache_features=True needs a model with encode() and refine()")
+    return alpha, bool(cache_features)
+
+
+def encode_first(model, ft, R, rows, K):
+    """``cache_features``, the first frame of a sequence: ``ft["frame"]``
+    encoded into ``rows`` of the feature ring.  The first call allocates the
+    ring of R rows and the gathered batch of K pairs from the features'
+    shapes and dtype."""
+    from ..ops import to_nhwc
+    f, c = model.encode(ft["frame"])
+    f, c = to_nhwc(f), to_nhwc(c)
+    if "ring_f" not in ft:
+        if f.dtype != c.dtype:
+            raise ValueError(f"cache_features: encode() returned {f.dtype} features and {c.dtype} context")
+        for name, like, n in (("ring_f", f, R), ("ring_c", c, R), ("x", f, 3 * K), ("ctx", c, 2 * K)):
+            ft[name] = like.new_zeros((n,) + tuple(like.shape[1:]))
+    for row in rows:
+        ft["ring_f"][row].copy_(f[0])
+        ft["ring_c"][row].copy_(c[0])
+
+
+def encode_and_gather(model, ft):
+    """``cache_features``, every later frame: ``ft["frame"]`` encoded at batch
+    1, stored in the ring row ``ft["idx"][-1]`` and gathered with the rows
+    ``ft["idx"][:-1]`` -> (x, ctx) for ``model.refine`` (ops.feature_ring_step)."""
+    from ..ops import feature_ring_step, from_nhwc, to_nhwc
+    f, c = model.encode(ft["frame"])
+    feature_ring_step(ft["ring_f"], ft["ring_c"], to_nhwc(f), to_nhwc(c), ft["idx"], ft["x"], ft["ctx"])
+    return from_nhwc(ft["x"]), from_nhwc(ft["ctx"])
+
+
+def image_buffer(shape, dev):
+    """A static image buffer: channels-last on the GPU, as the model's kernels read it."""
+    fmt = torch.channels_last if dev.type == "cuda" else torch.contiguous_format
+    return torch.zeros(tuple(shape), device=dev).contiguous(memory_format=fmt)
+
+
 class PointTrackServer:
     """Graphed STIR point tracker for serving on the GPU (HIP kernels)."""
 
@@ -161,7 +220,7 @@ class PointTrackServer:
         key = (tuple(image1.shape), tuple(pointlist.shape))
         st = self.graphs.get(key)
         if st is None:
-            st = self._capture(pointlist, image1, image2)
+            st = self._capture(dev, pointlist, image1, image2)
             self.graphs[key] = st
         st["p"].copy_(pointlist)
         st["i1"].copy_(image1)
@@ -169,20 +228,13 @@ class PointTrackServer:
         st["graph"].replay()
         return st["out"].clone()
 
-    def _capture(self, pointlist, image1, image2):
+    def _capture(self, dev, pointlist, image1, image2):
+        from ..runtime.graph import capture
         p = pointlist.detach().clone()
         i1 = image1.detach().clone().contiguous(memory_format=torch.channels_last)
         i2 = image2.detach().clone().contiguous(memory_format=torch.channels_last)
         tracker = RaftPointTrack(self.model, self.iters)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                tracker(p, i1, i2)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = tracker(p, i1, i2)
+        g, out = capture(dev, lambda: tracker(p, i1, i2))
         return {"graph": g, "p": p, "i1": i1, "i2": i2, "out": out}
 
 
@@ -204,10 +256,12 @@ class SequenceTracker:
 
     On the GPU the model forward, the point sampling and the forward
     interpolation are one captured hipGraph per (frame shape, N) over static
-    buffers.  A frame is uploaded once: between steps the graph's ``image2``
-    buffer is copied into ``image1`` on the device, and the new init into the
+    buffers.  A frame is uploaded once: between steps the ``image2`` buffer is
+    copied into ``image1`` on the device (the two belong to the frame shape,
+    so N may change within a sequence), and the new init into the
     ``flow_init`` buffer.  With frames and points already on the device no step
-    synchronises with the host.  On a CPU model the same loop runs eagerly.
+    synchronises with the host.  On a CPU model the same step runs on the same
+    buffers, eagerly.
 
     ``fb_check=True`` adds a visibility to every position.  A step is then::
 
@@ -248,22 +302,17 @@ class SequenceTracker:
         self.iters = iters
         self.warm_start = warm_start
         self.fb_check = fb_check
-        self.fb_alpha = (float(fb_alpha[0]), float(fb_alpha[1]))
-        if not (self.fb_alpha[0] >= 0 and self.fb_alpha[1] >= 0):
-            raise ValueError(f"fb_alpha must be two numbers >= 0, got {fb_alpha}")
-        self.cache_features = bool(cache_features)
-        if self.cache_features and not (hasattr(model, "encode") and hasattr(model, "refine")):
-            raise ValueError("cache_features=True needs a model with encode() and refine()")
+        self.fb_alpha, self.cache_features = check_tracker_options(model, fb_alpha, cache_features)
         self.graphs = {}
-        self._features = {}  # cache_features: frame shape -> the feature ring and the first frame's graph
+        self._frames = {}  # frame shape -> the frame buffers or the feature ring, and the zero init
         self._wkey = None
         self.reset()
 
     def reset(self):
         """Forget the previous frame, the points and the init."""
-        self._t = 0            # frames seen (cache_features: the ring row is t % 2)
+        self._t = 0            # frames seen (cache_features: frame t lives in ring row t % 2)
         self._next = None      # the init of the next step: (1,2,h,w), or (2,2,h,w) with fb_check
-        self._prev = None      # previous frame (on the GPU: the image2 buffer it was uploaded to)
+        self._shape = None     # the frame shape of the running sequence
         self.points = None
         self.flow_low = self.flow_up = self.flow_init = self.next_init = None
         self.flow_bw_low = self.flow_bw_up = self.flow_bw_init = self.next_bw_init = None
@@ -271,25 +320,58 @@ class SequenceTracker:
 
     @torch.no_grad()
     def step(self, frame, points=None):
-        if frame.dim() != 4 or frame.shape[0] != 1 or frame.shape[1] != 3:
-            raise ValueError(f"frame must be (1,3,H,W), got {tuple(frame.shape)}")
-        if frame.shape[-2] % 8 or frame.shape[-1] % 8:
-            raise ValueError(f"frame height and width must be multiples of 8, got {tuple(frame.shape[-2:])}")
-        if self._prev is not None and tuple(self._prev.shape) != tuple(frame.shape):
-            raise ValueError(f"frame shape changed within a sequence: {tuple(self._prev.shape)} -> "
-                             f"{tuple(frame.shape)} (call reset())")
+        """The feature ring or the pair of frame buffers belongs to the frame
+        shape, so that it outlives a change of N within a sequence; the step's
+        graph and its points and init buffers belong to (frame shape, N)."""
+        from ..runtime.graph import capture
+        from ..runtime.weights import refresh_if_moved
+        check_step_inputs(frame, self._shape, points)
         if points is None:
             points = self.points
         if points is None:
             raise ValueError("the first step of a sequence needs points")
-        if points.dim() != 3 or points.shape[0] != 1 or points.shape[2] != 2:
-            raise ValueError(f"points must be (1,N,2), got {tuple(points.shape)}")
         dev = next(self.model.parameters()).device
+        gpu = dev.type == "cuda"
+        if gpu:
+            self._wkey = refresh_if_moved(self.model, self._wkey)
+        shape = tuple(frame.shape)
+        ft = self._frames.get(shape)
+        if ft is None:
+            ft = self._frames[shape] = self._frame_state(dev, frame)
+        if self._t == 0:
+            ft["frame"].copy_(frame)
+            if self.cache_features:  # encoded into ring row 0, on the GPU by a small graph of its own
+                if gpu and ft["graph0"] is None:
+                    ft["graph0"], _ = capture(dev, lambda: encode_first(self.model, ft, 2, (0,), 1))
+                ft["graph0"].replay() if gpu else encode_first(self.model, ft, 2, (0,), 1)
+            self._shape, self._next, self._t = shape, ft["zero"], 1
+            return self._first(points.to(dev, torch.float32).clone())
+        key = (shape, points.shape[1]) + (("cache_features",) if self.cache_features else ())
+        st = self.graphs.get(key)
+        if st is None:
+            st = self.graphs[key] = {"p": torch.zeros(1, points.shape[1], 2, device=dev), "frames": ft,
+                                     "init": torch.zeros_like(ft["zero"]), "sgn": self._sgn(dev), "graph": None}
         if self.cache_features:
-            return self._step_cached(dev, frame, points)
-        if dev.type == "cuda":
-            return self._step_graphed(dev, frame, points)
-        return self._step_eager(dev, frame, points)
+            ft["idx"].copy_(ft["idx_table"][(self._t - 1) % 2])
+        else:
+            ft["prev"].copy_(ft["frame"])  # on the device: a frame is uploaded once
+        ft["frame"].copy_(frame)
+        st["p"].copy_(points)
+        st["init"].copy_(self._next)
+        if gpu and st["graph"] is None:
+            # captured on the step's own inputs: the warm-up runs write the ring row that this step writes
+            st["graph"], st["outs"] = capture(dev, lambda: self._run(st))
+        if gpu:
+            st["graph"].replay()
+            lo, up, out, err, ok, nxt = st["outs"]
+        else:
+            lo, up, out, err, ok, nxt = self._run(st)
+        self._t += 1
+        self.points = out.clone()
+        if self.fb_check:
+            self.fb_err, self.visible = err.clone(), ok.clone()
+        self._publish(st["init"], lo, up, nxt if self.warm_start else ft["zero"])
+        return self.points
 
     @torch.no_grad()
     def track(self, frames, points, return_visibility: bool = False):
@@ -320,10 +402,6 @@ class SequenceTracker:
         from ..ops import fb_consistency
         return fb_consistency(self.flow_up, self.flow_bw_up, *self.fb_alpha)
 
-    def _init_like(self, frame, dev):
-        # both directions' inits in one tensor with fb_check: forward first
-        return torch.zeros(2 if self.fb_check else 1, 2, frame.shape[-2] // 8, frame.shape[-1] // 8, device=dev)
-
     def _first(self, points):
         """Bookkeeping of the first step of a sequence; ``self._next`` is set."""
         self.points = points
@@ -342,13 +420,38 @@ class SequenceTracker:
             self.flow_bw_init, self.flow_bw_low, self.flow_bw_up, self.next_bw_init = (
                 init[1:2], lo[1:2], up[1:2], nxt[1:2])
 
-    def _forward(self, i1, i2, p, init, sgn):
-        """One pair: (flow_low, flow_up, new points, fb_err, visible, next init)."""
-        if not self.fb_check:
-            lo, up = self.model(i1, i2, iters=self.iters, flow_init=init, test_mode=True)
+    def _frame_state(self, dev, frame):
+        """What belongs to a frame shape: the new frame's buffer, one zero init
+        (never written: both directions in one tensor with fb_check, forward
+        first), and the previous frame's buffer or, with ``cache_features``,
+        what the feature ring needs (the ring itself comes with its first frame)."""
+        ft = {"frame": image_buffer(frame.shape, dev),
+              "zero": torch.zeros(2 if self.fb_check else 1, 2, frame.shape[-2] // 8, frame.shape[-1] // 8, device=dev)}
+        if self.cache_features:
+            # [source row, row written] of an odd and of an even step: frame t lives in row t % 2
+            ft.update({"idx_table": torch.tensor([[0, 1], [1, 0]], dtype=torch.int32, device=dev),
+                       "idx": torch.tensor([0, 1], dtype=torch.int32, device=dev), "graph0": None})
         else:
-            lo, up = self.model(i1, i2, iters=self.iters, flow_init=init, test_mode=True, bidirectional=True)
-        return self._follow(lo, up, p, sgn)
+            ft["prev"] = torch.zeros_like(ft["frame"])
+        return ft
+
+    def _run(self, st):
+        """One pair on the static buffers: (flow_low, flow_up, new points,
+        fb_err, visible, next init).  The two modes differ in how the flows
+        are obtained only."""
+        ft = st["frames"]
+        if self.cache_features:
+            x, ctx = encode_and_gather(self.model, ft)
+            if self.fb_check:
+                lo, up = self.model.refine(x[:2], x[1:], ctx, iters=self.iters, flow_init=st["init"])
+            else:
+                lo, up = self.model.refine(x[0:1], x[1:2], ctx[0:1], iters=self.iters, flow_init=st["init"])
+        elif self.fb_check:
+            lo, up = self.model(ft["prev"], ft["frame"], iters=self.iters, flow_init=st["init"], test_mode=True,
+                                bidirectional=True)
+        else:
+            lo, up = self.model(ft["prev"], ft["frame"], iters=self.iters, flow_init=st["init"], test_mode=True)
+        return self._follow(lo, up, st["p"], st["sgn"])
 
     def _follow(self, lo, up, p, sgn):
         """The points through the flows of one pair, and the next init."""
@@ -363,168 +466,3 @@ class SequenceTracker:
 
     def _sgn(self, dev):
         return torch.tensor([1.0, -1.0], device=dev).view(2, 1, 1, 1) if self.fb_check else None
-
-    def _step_eager(self, dev, frame, points):
-        frame = frame.to(dev, torch.float32)
-        points = points.to(dev, torch.float32)
-        if self._prev is None:
-            self._prev, self._next = frame, self._init_like(frame, dev)
-            return self._first(points.clone())
-        init = self._next
-        lo, up, self.points, self.fb_err, self.visible, nxt = self._forward(self._prev, frame, points, init,
-                                                                           self._sgn(dev))
-        self._publish(init, lo, up, nxt if self.warm_start else self._init_like(frame, dev))
-        self._prev = frame
-        return self.points
-
-    def _step_graphed(self, dev, frame, points):
-        from ..runtime.weights import refresh_all, weights_key
-        wkey = weights_key(self.model)
-        if self._wkey is not None and wkey != self._wkey:
-            refresh_all(self.model)  # weights moved since capture: re-pack into the captured storage
-        self._wkey = wkey
-        key = (tuple(frame.shape), points.shape[1])
-        st = self.graphs.get(key)
-        if st is None:
-            st = self.graphs[key] = self._capture(dev, frame, points)
-        if self._prev is None:
-            st["i2"].copy_(frame)
-            self._prev, self._next = st["i2"], st["zero"]
-            return self._first(points.to(dev, torch.float32).clone())
-        st["i1"].copy_(self._prev)
-        st["i2"].copy_(frame)
-        st["p"].copy_(points)
-        st["init"].copy_(self._next)
-        st["graph"].replay()
-        self._prev, self.points = st["i2"], st["out"].clone()
-        if self.fb_check:
-            self.fb_err, self.visible = st["err"].clone(), st["ok"].clone()
-        self._publish(st["init"], st["lo"], st["up"], st["next"] if self.warm_start else st["zero"])
-        return self.points
-
-    def _run(self, st):
-        return self._forward(st["i1"], st["i2"], st["p"], st["init"], st["sgn"])
-
-    def _capture(self, dev, frame, points):
-        st = {"p": torch.zeros(1, points.shape[1], 2, device=dev),
-              "i1": torch.zeros(tuple(frame.shape), device=dev).contiguous(memory_format=torch.channels_last),
-              "init": self._init_like(frame, dev), "zero": self._init_like(frame, dev),
-              "sgn": self._sgn(dev)}
-        st["i2"] = torch.zeros_like(st["i1"])
-        st["i1"].copy_(frame)
-        st["i2"].copy_(frame)
-        st["p"].copy_(points)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._run(st)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            st["lo"], st["up"], st["out"], st["err"], st["ok"], st["next"] = self._run(st)
-        st["graph"] = g
-        return st
-
-    # ---------------------------------------------------------- cache_features
-    def _run_first(self, ft):
-        """The first frame of a sequence: encoded into row 0.  The first call
-        for a frame shape allocates the ring and the gathered batch from the
-        features' shapes and dtype."""
-        from ..ops import to_nhwc
-        f, c = self.model.encode(ft["frame"])
-        f, c = to_nhwc(f), to_nhwc(c)
-        if "ring_f" not in ft:
-            if f.dtype != c.dtype:
-                raise ValueError(f"cache_features: encode() returned {f.dtype} features and {c.dtype} context")
-            ft["ring_f"], ft["ring_c"] = f.new_zeros((2,) + tuple(f.shape[1:])), c.new_zeros((2,) + tuple(c.shape[1:]))
-            ft["x"], ft["ctx"] = f.new_zeros((3,) + tuple(f.shape[1:])), c.new_zeros((2,) + tuple(c.shape[1:]))
-        ft["ring_f"][0].copy_(f[0])
-        ft["ring_c"][0].copy_(c[0])
-
-    def _run_cached(self, st):
-        from ..ops import feature_ring_step, from_nhwc, to_nhwc
-        ft = st["features"]
-        f, c = self.model.encode(ft["frame"])
-        feature_ring_step(ft["ring_f"], ft["ring_c"], to_nhwc(f), to_nhwc(c), ft["idx"], ft["x"], ft["ctx"])
-        x, ctx = from_nhwc(ft["x"]), from_nhwc(ft["ctx"])
-        if self.fb_check:
-            lo, up = self.model.refine(x[:2], x[1:], ctx, iters=self.iters, flow_init=st["init"])
-        else:
-            lo, up = self.model.refine(x[0:1], x[1:2], ctx[0:1], iters=self.iters, flow_init=st["init"])
-        return self._follow(lo, up, st["p"], st["sgn"])
-
-    @staticmethod
-    def _graphed(dev, fn):
-        """fn() twice on a side stream, then captured: (graph, fn's outputs)."""
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                fn()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = fn()
-        return g, out
-
-    def _step_cached(self, dev, frame, points):
-        """The feature ring belongs to the frame shape, so that it outlives a
-        change of N within a sequence; the step's graph and its points and
-        init buffers belong to (frame shape, N), as without the cache."""
-        gpu = dev.type == "cuda"
-        if gpu:
-            from ..runtime.weights import refresh_all, weights_key
-            wkey = weights_key(self.model)
-            if self._wkey is not None and wkey != self._wkey:
-                refresh_all(self.model)  # weights moved since capture: re-pack into the captured storage
-            self._wkey = wkey
-        shape = tuple(frame.shape)
-        ft = self._features.get(shape)
-        if ft is None:
-            fmt = torch.channels_last if gpu else torch.contiguous_format
-            ft = self._features[shape] = {
-                "frame": torch.zeros(shape, device=dev).contiguous(memory_format=fmt),
-                # [source row, row written] of an odd and of an even step: frame t lives in row t % 2
-                "idx_table": torch.tensor([[0, 1], [1, 0]], dtype=torch.int32, device=dev),
-                "idx": torch.tensor([0, 1], dtype=torch.int32, device=dev), "graph0": None}
-        ft["frame"].copy_(frame)
-        if self._prev is None:
-            if gpu and ft["graph0"] is None:
-                ft["graph0"], _ = self._graphed(dev, lambda: self._run_first(ft))
-            if gpu:
-                ft["graph0"].replay()
-            else:
-                self._run_first(ft)
-            self._prev, self._next, self._t = ft["frame"], self._zero_cached(dev, frame), 1
-            return self._first(points.to(dev, torch.float32).clone())
-        key = (shape, points.shape[1], "cache_features")
-        st = self.graphs.get(key)
-        if st is None:
-            st = self.graphs[key] = {"p": torch.zeros(1, points.shape[1], 2, device=dev), "features": ft,
-                                     "init": self._init_like(frame, dev), "zero": self._zero_cached(dev, frame),
-                                     "sgn": self._sgn(dev), "graph": None}
-        ft["idx"].copy_(ft["idx_table"][(self._t - 1) % 2])
-        st["p"].copy_(points)
-        st["init"].copy_(self._next)
-        if gpu and st["graph"] is None:
-            # captured on the step's own inputs: the warm-up runs write the ring row that this step writes
-            st["graph"], st["outs"] = self._graphed(dev, lambda: self._run_cached(st))
-        if gpu:
-            st["graph"].replay()
-            lo, up, out, err, ok, nxt = st["outs"]
-        else:
-            lo, up, out, err, ok, nxt = self._run_cached(st)
-        self._t += 1
-        self.points = out.clone()
-        if self.fb_check:
-            self.fb_err, self.visible = err.clone(), ok.clone()
-        self._publish(st["init"], lo, up, nxt if self.warm_start else st["zero"])
-        return self.points
-
-    def _zero_cached(self, dev, frame):
-        """One zero init per frame shape (never written)."""
-        ft = self._features[tuple(frame.shape)]
-        if "zero" not in ft:
-            ft["zero"] = self._init_like(frame, dev)
-        return ft["zero"]

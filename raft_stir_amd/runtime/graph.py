@@ -15,7 +15,24 @@ from typing import Dict, Tuple
 
 import torch
 
-from .weights import bump, refresh_all, repack_in_graph, weights_key
+from .weights import bump, refresh_if_moved, repack_in_graph, weights_key
+
+
+def capture(dev, fn, warmup=2, pool=None):
+    """The inference capture recipe: ``fn()`` ``warmup`` times on a side
+    stream, joined, then recorded into a hipGraph -> (graph, fn's outputs).
+    ``fn`` reads and writes static device buffers only; its outputs are owned
+    by the graph and rewritten by every replay."""
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.current_stream(dev).wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, pool=pool):
+        out = fn()
+    return graph, out
 
 
 class GraphedInference:
@@ -28,15 +45,8 @@ class GraphedInference:
         self.i1 = torch.zeros(shape, device=dev).contiguous(memory_format=torch.channels_last)
         self.i2 = torch.zeros_like(self.i1)
         self.flow_init = torch.zeros(B, 2, H // 8, W // 8, device=dev) if warm_start else None
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.no_grad(), torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._run()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph, pool=pool):
-            self.out = self._run()
+        with torch.no_grad():
+            self.graph, self.out = capture(dev, self._run, warmup, pool)
         self._wkey = weights_key(model)
 
     def _run(self):
@@ -52,10 +62,7 @@ class GraphedInference:
                 self.flow_init.zero_()
             else:
                 self.flow_init.copy_(flow_init)
-        key = weights_key(self.model)
-        if key != self._wkey:  # weights moved since capture: re-pack into the captured storage
-            refresh_all(self.model)
-            self._wkey = key
+        self._wkey = refresh_if_moved(self.model, self._wkey)
         self.graph.replay()
         return self.out
 

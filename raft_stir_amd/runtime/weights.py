@@ -74,4 +74,14 @@ def weights_key(model) -> tuple:
     return (generation(),) + tuple((p.data_ptr(), p._version) for p in model.parameters())
 
 
+def refresh_if_moved(model, last):
+    """Before a replay of a graph captured on ``model``: re-pack the weights
+    into the captured storage if they moved since ``last``, the key this
+    returned before (None: nothing captured yet).  Returns the key of now."""
+    key = weights_key(model)
+    if last is not None and key != last:
+        refresh_all(model)
+    return key
+
+
 _HANDLE = register_optimizer_step_post_hook(bump)
