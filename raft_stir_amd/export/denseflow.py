@@ -11,6 +11,10 @@ in a planar ring on the device and advances all of them in one launch per
 step (ops.dense_multi_flow_step, csrc/dense_flow.hip).  The result is a
 long-term flow field ``anchor -> t`` with a visibility map, and points can be
 asked for after the sequence has run (:meth:`DenseMultiFlowTracker.query`).
+The inverse map, which anchor pixel sits on every cell of frame t, comes from
+forward splatting (:meth:`DenseMultiFlowTracker.splat`, ops.forward_splat)
+and carries labels of the first frame through the video
+(:meth:`DenseMultiFlowTracker.warp_labels`); it is ATen on the CPU so far.
 """
 from __future__ import annotations
 
@@ -104,19 +108,70 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         return reference.dense_query(self.pos, self.score, points.to(self.pos.device, torch.float32))
 
     @torch.no_grad()
-    def track(self, frames):
+    def splat(self, values=None, footprint: int = 2, fill: float = 0.0):
+        """The inverse map of the current frame, by forward splatting
+        (ops.forward_splat on ``pos`` and ``score``): for every cell of frame
+        t the anchor pixel that sits there.  values (1,C,H,W) or None ->
+        (src_index (1,1,H,W) int32, -1 at holes; covered (1,1,H,W) bool;
+        inv_pos (1,2,H,W), the cell's position in the anchor frame, NaN at
+        holes; out (1,C,H,W) fp32, ``values`` carried along and ``fill`` at
+        holes, None without values).  On the first frame it is the identity:
+        every cell is covered by itself.  The tensors are the caller's own.
+        A tracker on the CPU only: there is no HIP kernel for the splat yet,
+        and on the GPU this raises NotImplementedError."""
+        from ..ops import forward_splat
+        if self.pos is None:
+            raise ValueError("splat() needs a step first")
+        if values is not None:
+            values = values.to(self.pos.device)
+        return forward_splat(self.pos, self.score, values, footprint=footprint, fill=fill)
+
+    @torch.no_grad()
+    def warp_labels(self, labels, footprint: int = 2, fill=0):
+        """Carry labels of the anchor frame into the current frame.  labels
+        (H,W), (1,1,H,W) or (1,C,H,W), of any dtype -> (warped, of labels'
+        shape and dtype: at every cell the label of the anchor pixel that
+        :meth:`splat` finds there, ``fill`` at holes; covered (1,1,H,W) bool).
+        fp32 labels are gathered by the splat itself; every other dtype by one
+        gather along ``src_index``, so integer labels stay exact.  As
+        :meth:`splat`, on a CPU tracker only."""
+        if self.pos is None:
+            raise ValueError("warp_labels() needs a step first")
+        H, W = self.pos.shape[-2:]
+        shape = tuple(labels.shape)
+        if not (shape == (H, W) or (labels.dim() == 4 and shape[0] == 1 and shape[1] >= 1 and shape[2:] == (H, W))):
+            raise ValueError(f"labels must be (H,W), (1,1,H,W) or (1,C,H,W) with H, W = {(H, W)}, got {shape}")
+        lab = labels.to(self.pos.device).reshape(1, -1, H, W)
+        if lab.dtype == torch.float32:
+            _, covered, _, out = self.splat(lab, footprint=footprint, fill=float(fill))
+            return out.reshape(shape), covered
+        src, covered, _, _ = self.splat(None, footprint=footprint)
+        got = lab.reshape(-1, H * W).index_select(1, src.reshape(-1).long().clamp_(min=0)).reshape(1, -1, H, W)
+        hole = torch.full((), fill, dtype=lab.dtype, device=lab.device)
+        return torch.where(covered, got, hole).reshape(shape), covered
+
+    @torch.no_grad()
+    def track(self, frames, labels=None, footprint: int = 2, fill=0):
         """frames (T,1,3,H,W) or a list of (1,3,H,W) -> (flows (T,2,H,W), the
         long-term flow 0 -> t of every pixel, visible (T,1,H,W) bool);
-        ``flows[0] == 0``."""
+        ``flows[0] == 0``.  With ``labels`` of the first frame
+        (:meth:`warp_labels`) two more: the labels warped into every frame,
+        (T,) + labels.shape, and covered (T,1,H,W) bool."""
         if len(frames) < 1:
             raise ValueError("track() needs at least one frame")
         self.reset()
-        flows, vis = [], []
+        flows, vis, warped, cov = [], [], [], []
         for t in range(len(frames)):
             self.step(frames[t])
             flows.append(self.flow[0])
             vis.append(self.visible[0].clone())
-        return torch.stack(flows), torch.stack(vis)
+            if labels is not None:
+                w, c = self.warp_labels(labels, footprint=footprint, fill=fill)
+                warped.append(w)
+                cov.append(c[0])
+        if labels is None:
+            return torch.stack(flows), torch.stack(vis)
+        return torch.stack(flows), torch.stack(vis), torch.stack(warped), torch.stack(cov)
 
     # ------------------------------------------------------------------- state
     def _history(self, dev, frame, points):

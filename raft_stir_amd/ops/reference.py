@@ -419,3 +419,76 @@ def dense_query(pos, score, points):
     inf = torch.full_like(x, float("inf"))
     worst = torch.where(inside, worst, inf)
     return out, worst < inf, worst
+
+
+_SPLAT_HOLE = torch.iinfo(torch.int64).max
+
+
+def forward_splat(pos, score, values=None, footprint: int = 2, fill: float = 0.0):
+    """Forward splatting of the anchor frame into the frame a dense track
+    field points to: for every cell of the target frame, which anchor pixel
+    sits there.  This docstring is the rule.  pos (1,2,H,W), channel 0
+    = x; score (1,1,H,W), finite iff visible (as DenseMultiFlowTracker stores
+    it); values (1,C,H,W) or None.
+
+    Anchor pixel n = y*W + x is a source iff ``0 <= score < +inf`` and
+    ``-1 < x' < W and -1 < y' < H`` (NaN fails both).  Its nearest cell is
+    ``(round(x'), round(y'))``, halves to even.  With ``footprint=1`` it offers
+    itself to that cell; with ``footprint=2`` to the up-to-four cells
+    ``(floor x' + {0,1}, floor y' + {0,1})`` whose bilinear weight (the fp32
+    products of S in csrc/fb_device.h) is not 0: the nearest cell in class 0,
+    the others in class 1.  Offers to cells outside the image are dropped.  A
+    cell takes the offer of smallest ``(class, score + 0.0, n)``; a cell
+    without an offer is a hole.  The minimum is taken over one packed integer
+    per offer, (class, the score's bits, n) from the top, so it does not depend
+    on any order.
+
+    -> (src_index (1,1,H,W) int32, -1 at holes; covered (1,1,H,W) bool;
+    inv_pos (1,2,H,W): ``grid(n) + (cell - pos[n])``, the cell's position in
+    the anchor frame, NaN at holes; out (1,C,H,W): ``values[:, n]``, ``fill``
+    at holes, None without values).  No host synchronisation."""
+    if footprint not in (1, 2):
+        raise ValueError(f"forward_splat: footprint must be 1 or 2, got {footprint}")
+    _, _, H, W = pos.shape
+    N, dev = H * W, pos.device
+    x, y = pos[0, 0].reshape(N).float(), pos[0, 1].reshape(N).float()
+    s = score.reshape(N).float() + 0.0  # -0 -> +0
+    inf = torch.full_like(s, float("inf"))
+    src = (s >= 0) & (s < inf) & (x > -1) & (x < W) & (y > -1) & (y < H)  # before any int conversion
+    zero = torch.zeros_like(x)
+    xs, ys = torch.where(src, x, zero), torch.where(src, y, zero)
+    nx, ny = torch.round(xs).long(), torch.round(ys).long()
+    n = torch.arange(N, device=dev)
+    # score >= 0: its bit pattern is ordered like the float and bit 31 is free
+    base = (torch.where(src, s, zero).view(torch.int32).long() << 31) | n
+    if footprint == 1:
+        offers = [(nx, ny, src, base)]
+    else:
+        x0, y0 = torch.floor(xs), torch.floor(ys)
+        wx, wy = xs - x0, ys - y0
+        ux, uy = 1 - wx, 1 - wy
+        xi0, yi0 = x0.long(), y0.long()
+        offers = []
+        for dx, dy, w in ((0, 0, ux * uy), (1, 0, wx * uy), (0, 1, ux * wy), (1, 1, wx * wy)):
+            xi, yi = xi0 + dx, yi0 + dy
+            far = ((xi != nx) | (yi != ny)).long()
+            offers.append((xi, yi, src & (w != 0), base | (far << 62)))
+    keys = torch.full((N,), _SPLAT_HOLE, dtype=torch.int64, device=dev)
+    hole = torch.full_like(base, _SPLAT_HOLE)
+    for xi, yi, use, key in offers:
+        use = use & (xi >= 0) & (xi < W) & (yi >= 0) & (yi < H)
+        cell = yi.clamp(0, H - 1) * W + xi.clamp(0, W - 1)
+        keys.scatter_reduce_(0, cell, torch.where(use, key, hole), "amin")  # an offer not made: the hole key
+    covered = keys != _SPLAT_HOLE
+    win = torch.where(covered, keys & (2 ** 31 - 1), torch.zeros_like(keys))
+    src_index = torch.where(covered, win, torch.full_like(win, -1)).to(torch.int32)
+    cy = torch.div(n, W, rounding_mode="floor")
+    gx, gy = (n - cy * W).float(), cy.float()
+    nan = torch.full_like(x, float("nan"))
+    inv = torch.stack([torch.where(covered, gx[win] + (gx - x[win]), nan),
+                       torch.where(covered, gy[win] + (gy - y[win]), nan)])
+    out = None
+    if values is not None:
+        v = values.float().reshape(-1, N)
+        out = torch.where(covered, v[:, win], torch.full_like(v[:, :1], fill)).reshape(1, -1, H, W)
+    return src_index.reshape(1, 1, H, W), covered.reshape(1, 1, H, W), inv.reshape(1, 2, H, W), out

@@ -5,7 +5,8 @@ whole sequence, with RAFT's video warm start).
     python track.py --model M [--small --mixed_precision --iters 12 --no_warm_start] \
         [--fb_check [--fb_alpha A1 A2]] [--deltas 1 4 16 inf] [--cache_features] \
         --path demo-frames --points points.txt --out tracks.csv
-    python track.py --model M --dense --deltas 1 4 16 inf [--points points.txt] --path demo-frames --out tracks/
+    python track.py --model M --dense --deltas 1 4 16 inf [--points points.txt] [--labels mask.png] \
+        --path demo-frames --out tracks/
 
 ``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
 CSV has a ``frame,point,x,y`` row for every point in every frame (frame 0 holds
@@ -37,6 +38,14 @@ the flow between unpadded coordinates.  ``--dense`` with ``--points`` writes the
 eight-column CSV ``tracks.csv`` into that directory as well, the points read
 from the dense field after every step (``DenseMultiFlowTracker.query``);
 ``fb_err`` and ``delta`` are then those of the pixel nearest to the point.
+
+``--dense --labels mask.png [--splat_footprint {1,2}]`` carries a label image
+of the first frame (8- or 16-bit, one channel, the first frame's size) through
+the video by forward splatting (``ops.forward_splat``, computed on the host): per
+frame t ``labels_TTTT.png``, in the mask's bit depth with 0 where no pixel of
+the first frame lands, and ``covered_TTTT.png`` (255: some pixel lands there).
+The mask is padded like the frames, with label 0, and the images are cropped
+back.
 """
 import argparse
 import csv
@@ -54,6 +63,7 @@ from raft_stir_amd.data.frame_utils import writeFlow  # noqa: E402
 from raft_stir_amd.export.denseflow import DenseMultiFlowTracker  # noqa: E402
 from raft_stir_amd.export.multiflow import MultiFlowTracker  # noqa: E402
 from raft_stir_amd.export.pointtrack import SequenceTracker  # noqa: E402
+from raft_stir_amd.ops import forward_splat  # noqa: E402
 from raft_stir_amd.utils.padder import InputPadder  # noqa: E402
 
 
@@ -107,9 +117,29 @@ def track_dense(args, model, images, pts, dev):
     padder = InputPadder(load_image(images[0], dev).shape)
     shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
     points = None if pts is None else torch.from_numpy(pts).to(dev)[None] + shift
+    labels = None
+    if args.labels:
+        mask = np.asarray(Image.open(args.labels))
+        if mask.ndim != 2 or mask.dtype not in (np.uint8, np.uint16):
+            raise ValueError(f"{args.labels}: an 8- or 16-bit single-channel PNG expected, got {mask.dtype} "
+                             f"{mask.shape}")
+        if mask.shape != (padder.ht, padder.wd):
+            raise ValueError(f"{args.labels}: the first frame's size {(padder.ht, padder.wd)} expected, got "
+                             f"{mask.shape}")
+        # the padding carries label 0, not a replicated border; the labels stay on the host
+        labels = torch.nn.functional.pad(torch.from_numpy(mask.astype(np.int32)), padder._pad, value=0)
     cols = [[], [], [], [], []]
     for t, f in enumerate(images):
         tracker.step(padder.pad(load_image(f, dev))[0])
+        if labels is not None:
+            # on the host, where the images are written anyway: forward splatting has no HIP kernel yet
+            src, covered, _, _ = forward_splat(tracker.pos.cpu(), tracker.score.cpu(), footprint=args.splat_footprint)
+            warped = labels.reshape(-1)[src[0, 0].long().clamp(min=0)]
+            warped = torch.where(covered[0, 0], warped, torch.zeros_like(warped))
+            warped = padder.unpad(warped).numpy().astype(mask.dtype)
+            Image.fromarray(warped).save(os.path.join(args.out, f"labels_{t:04d}.png"))
+            covered = padder.unpad(covered)[0, 0].numpy()
+            Image.fromarray(covered.astype(np.uint8) * 255).save(os.path.join(args.out, f"covered_{t:04d}.png"))
         # a difference of two positions: the padding's shift cancels
         flow = padder.unpad(tracker.flow)[0].permute(1, 2, 0).cpu().numpy()
         vis = padder.unpad(tracker.visible)[0, 0].cpu().numpy()
@@ -124,6 +154,8 @@ def track_dense(args, model, images, pts, dev):
                                    tracker.delta.view(1, -1).gather(1, near))):
                 c.append(x)
     print(f"wrote {len(images)} flow fields and visibility maps to {args.out}")
+    if labels is not None:
+        print(f"wrote {len(images)} warped label images and coverage maps to {args.out}")
     if points is None:
         return None
     traj, err, vis, score, delta = (torch.cat(c).cpu().numpy() for c in cols)
@@ -199,9 +231,16 @@ def parse_args(argv=None):
     parser.add_argument("--dense", action="store_true",
                         help="with --deltas: track every pixel of the first frame and write a .flo and a visibility "
                              "image per frame into the directory --out (with --points: tracks.csv there too)")
+    parser.add_argument("--labels", metavar="MASK.png",
+                        help="with --dense: an 8- or 16-bit single-channel label image of the first frame; every "
+                             "frame's labels_TTTT.png and covered_TTTT.png go into the directory --out")
+    parser.add_argument("--splat_footprint", type=int, choices=(1, 2), default=2,
+                        help="with --labels: a pixel claims its nearest cell (1) or every cell it touches (2)")
     args = parser.parse_args(argv)
     if args.dense and not args.deltas:
         parser.error("--dense needs --deltas")
+    if args.labels and not args.dense:
+        parser.error("--labels needs --dense")
     if not args.dense and not args.points:
         parser.error("the following arguments are required: --points")
     return args
