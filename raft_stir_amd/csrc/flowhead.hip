@@ -14,10 +14,13 @@
 //             the 8 x 2 per-lane partial sums are reduced across the wave by
 //             a halving butterfly (17 shuffles instead of 96), then the
 //             coords epilogue: crd = src + bias + conv (EPI_FLOW semantics).
-//   dgrad   : one wave = 8 consecutive pixels; the fp32 flow gradient of the
-//             3 x 10 neighbourhood is wave-uniform (scalar loads), lane l
-//             produces channels [CPL*l, CPL*l + CPL) of each pixel's input
-//             gradient, masked by the hidden ReLU (EPI_RELU_BWD semantics).
+//   dgrad   : persistent waves, each walking 8-pixel row segments with its
+//             weights in registers; the fp32 flow gradient of a segment's
+//             3 x 10 neighbourhood is one vector load spread into
+//             wave-uniform operands by v_readlane, lane l produces channels
+//             [CPL*l, CPL*l + CPL) of each pixel's input gradient, masked by
+//             the hidden ReLU (EPI_RELU_BWD semantics); the next segment is
+//             fetched while the current one is computed.
 #include "common.h"
 
 namespace rs {
@@ -165,21 +168,56 @@ __global__ __launch_bounds__(256) void flowhead_fwd_kernel(const XT* __restrict_
   }
 }
 
+// The lane's CPL channels of one pixel as loaded (converted where they are
+// used: a prefetched pixel waits for memory at its use, not at its load).
+template <int CPL, typename T> struct rawv;
+template <> struct rawv<4, bf16_t> { typedef uint2 type; };
+template <> struct rawv<2, bf16_t> { typedef uint32_t type; };
+template <> struct rawv<4, float> { typedef float4 type; };
+template <> struct rawv<2, float> { typedef float2 type; };
+
+__device__ __forceinline__ void unpack(const uint2& u, float (&f)[4]) {
+  f[0] = bf2f((bf16_t)(u.x & 0xffffu));
+  f[1] = bf2f((bf16_t)(u.x >> 16));
+  f[2] = bf2f((bf16_t)(u.y & 0xffffu));
+  f[3] = bf2f((bf16_t)(u.y >> 16));
+}
+__device__ __forceinline__ void unpack(const uint32_t& u, float (&f)[2]) {
+  f[0] = bf2f((bf16_t)(u & 0xffffu));
+  f[1] = bf2f((bf16_t)(u >> 16));
+}
+__device__ __forceinline__ void unpack(const float4& u, float (&f)[4]) {
+  f[0] = u.x; f[1] = u.y; f[2] = u.z; f[3] = u.w;
+}
+__device__ __forceinline__ void unpack(const float2& u, float (&f)[2]) {
+  f[0] = u.x; f[1] = u.y;
+}
+
 // dflow: (B, 2, H, W) fp32; w: fp32 [2][9][Cin]; act: NHWC T hidden (ReLU output,
 // stride astr, offset aoff); out: NHWC T (stride ostr, offset ooff), Cin channels;
 // T = bf16, or fp32 (the fp32 training engine).
+//
+// Persistent waves: the grid is sized from the CU count (flowhead_dgrad_launch),
+// a wave loads its 18 x CPL weights once and walks the 8-pixel row segments
+// seg, seg + waves, ... .  The 3 x 10 x 2 flow-gradient neighbourhood of a
+// segment is ONE vector load (lane (r * 10 + c) * 2 + co holds its value,
+// zero outside the image) that v_readlane then spreads into wave-uniform
+// operands; it and the 8 activation loads of the NEXT segment are issued
+// before the current segment's arithmetic, so the wave computes and stores
+// while they are in flight.  Per output element the arithmetic is the tap
+// order and fma nesting of the one-segment-per-wave kernel this replaces.
 template <int CPL, typename T>
 __global__ __launch_bounds__(256) void flowhead_dgrad_kernel(const float* __restrict__ dflow,
                                                              const float* __restrict__ w, int B, int H, int W,
                                                              const T* __restrict__ act, int astr, int aoff,
                                                              T* __restrict__ out, int ostr, int ooff) {
   constexpr int CIN = 64 * CPL;
+  typedef typename rawv<CPL, T>::type RV;
   const int lane = threadIdx.x & 63;
-  const int segs_row = cdiv(W, PX);
-  const int seg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (seg >= B * H * segs_row) return;
-  const int br = seg / segs_row, x0 = (seg - br * segs_row) * PX;
-  const int b = br / H, y = br - b * H;
+  const int segs_row = cdiv(W, PX), nseg = B * H * segs_row;
+  const int nwave = gridDim.x * 4;
+  int seg = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (seg >= nseg) return;
   float wr[2][9][CPL];
 #pragma unroll
   for (int co = 0; co < 2; ++co)
@@ -188,48 +226,89 @@ __global__ __launch_bounds__(256) void flowhead_dgrad_kernel(const float* __rest
 #pragma unroll
       for (int j = 0; j < CPL; ++j) wr[co][t][j] = w[(co * 9 + t) * CIN + lane * CPL + j];
   // dx[q] = sum_{ty,tx} sum_co W[co][ty][tx] * dflow[q - (ty - 1, tx - 1)][co]
-  float g[3][PX + 2][2];  // dflow at rows y-1..y+1, columns x0-1..x0+PX (wave-uniform)
+  // this lane's slot of the neighbourhood: rows y-1..y+1, columns x0-1..x0+PX (lanes 60..63: none)
+  const int gq = lane >> 1, gco = lane & 1, gr = gq / (PX + 2), gc = gq - gr * (PX + 2);
   const size_t plane = (size_t)H * W;
+  float gn;      // the fetched segment's neighbourhood value of this lane
+  RV an[PX];     // ... and its hidden activations (ReLU mask)
+  auto fetch = [&](int s) {
+    const int br = s / segs_row, x0 = (s - br * segs_row) * PX;
+    const int b = br / H, y = br - b * H;
+    const int yy = y + gr - 1, xx = x0 + gc - 1;
+    const bool in = gr < 3 && yy >= 0 && yy < H && xx >= 0 && xx < W;
+    gn = in ? dflow[((size_t)b * 2 + gco) * plane + (size_t)yy * W + xx] : 0.f;
 #pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const int yy = y + r - 1;
-#pragma unroll
-    for (int c = 0; c < PX + 2; ++c) {
-      const int xx = x0 + c - 1;
-      const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-      const size_t o = (size_t)b * 2 * plane + (size_t)(in ? yy : 0) * W + (in ? xx : 0);
-      g[r][c][0] = in ? dflow[o] : 0.f;
-      g[r][c][1] = in ? dflow[o + plane] : 0.f;
+    for (int px = 0; px < PX; ++px) {
+      const int xc = x0 + px < W ? x0 + px : W - 1;
+      an[px] = *reinterpret_cast<const RV*>(act + ((size_t)(b * H + y) * W + xc) * astr + aoff + lane * CPL);
     }
+  };
+  fetch(seg);
+  for (;;) {
+    const int br = seg / segs_row, x0 = (seg - br * segs_row) * PX;
+    const int b = br / H, y = br - b * H;
+    const float gv = gn;
+    RV av[PX];
+#pragma unroll
+    for (int px = 0; px < PX; ++px) av[px] = an[px];
+    const int nxt = seg + nwave;
+    fetch(nxt < nseg ? nxt : nseg - 1);  // (the last trip fetches an in-range segment it does not use)
+    float g[3][PX + 2][2];  // wave-uniform; column c is read out when pixel c - 2 first needs it
+#pragma unroll
+    for (int px = 0; px < PX; ++px) {
+      if (x0 + px >= W) break;
+#pragma unroll
+      for (int c = px == 0 ? 0 : px + 2; c < px + 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int co = 0; co < 2; ++co)
+            g[r][c][co] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gv), (r * (PX + 2) + c) * 2 + co));
+      float acc[CPL];
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
+#pragma unroll
+      for (int ty = 0; ty < 3; ++ty)
+#pragma unroll
+        for (int tx = 0; tx < 3; ++tx) {
+          // output pixel (y - (ty-1), x - (tx-1)) = neighbourhood row 2 - ty, column px + 2 - tx
+          const float g0 = g[2 - ty][px + 2 - tx][0], g1 = g[2 - ty][px + 2 - tx][1];
+#pragma unroll
+          for (int j = 0; j < CPL; ++j)
+            acc[j] = fmaf(g0, wr[0][ty * 3 + tx][j], fmaf(g1, wr[1][ty * 3 + tx][j], acc[j]));
+        }
+      const size_t p = (size_t)(b * H + y) * W + x0 + px;
+      float af[CPL];
+      unpack(av[px], af);
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) acc[j] = af[j] > 0.f ? acc[j] : 0.f;
+      stc<CPL>(out + p * ostr + ooff + lane * CPL, acc);
+    }
+    if (nxt >= nseg) break;
+    seg = nxt;
   }
-  // the hidden activations of the PX pixels (ReLU mask), loaded up front
-  float av[PX][CPL];
-#pragma unroll
-  for (int px = 0; px < PX; ++px) {
-    const int xc = x0 + px < W ? x0 + px : W - 1;
-    ldc<CPL>(act + ((size_t)(b * H + y) * W + xc) * astr + aoff + lane * CPL, av[px]);
-  }
-#pragma unroll
-  for (int px = 0; px < PX; ++px) {
-    if (x0 + px >= W) break;
-    float acc[CPL];
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
-#pragma unroll
-    for (int ty = 0; ty < 3; ++ty)
-#pragma unroll
-      for (int tx = 0; tx < 3; ++tx) {
-        // output pixel (y - (ty-1), x - (tx-1)) = neighbourhood row 2 - ty, column px + 2 - tx
-        const float g0 = g[2 - ty][px + 2 - tx][0], g1 = g[2 - ty][px + 2 - tx][1];
-#pragma unroll
-        for (int j = 0; j < CPL; ++j)
-          acc[j] = fmaf(g0, wr[0][ty * 3 + tx][j], fmaf(g1, wr[1][ty * 3 + tx][j], acc[j]));
-      }
-    const size_t p = (size_t)(b * H + y) * W + x0 + px;
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) acc[j] = av[px][j] > 0.f ? acc[j] : 0.f;
-    stc<CPL>(out + p * ostr + ooff + lane * CPL, acc);
-  }
+}
+
+// grid-size override of the dgrad (RS_FH_BLOCKS; 0: blocks per CU x CU count)
+int g_dgrad_blocks = 0;
+
+// Blocks per CU: what the instance's registers keep resident, at most 4.
+// Measured at 96 x 46 x 62, cin 256, bf16 (profiles/head_batch/README.md): 1
+// block per CU 75.6 us, 2: 59.8, 3: 58.1, 4: 58.0, 6: 59.8, 8: 61.2, 16: 63.4.
+// The 3 of the fp32 cin-256 instance is not timed: it follows from its 154
+// VGPRs (3 waves per SIMD).  A grid beyond the resident blocks still computes
+// the same: the rest run afterwards.
+template <int CPL, typename T>
+int dgrad_grid(int segs) {
+  // the current device's CU count, asked for per call (a plain attribute read:
+  // nothing cached, so nothing shared between threads or devices)
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+    cus = 256;
+  constexpr int per_cu = (CPL == 4 && sizeof(T) == 4) ? 3 : 4;
+  const int want = g_dgrad_blocks > 0 ? g_dgrad_blocks : cus * per_cu;
+  return max(1, min(want, cdiv(segs, 4)));
 }
 
 }  // namespace fh
@@ -257,29 +336,32 @@ void flowhead_fwd_launch(const void* x, int xstr, int xoff, int cin, const float
                        crd, src);
 }
 
+void flowhead_set_dgrad_blocks(int n) { fh::g_dgrad_blocks = n > 0 ? n : 0; }
+int flowhead_dgrad_blocks() { return fh::g_dgrad_blocks; }
+
 void flowhead_dgrad_launch(const float* dflow, const float* w, int cin, int B, int H, int W, const void* act,
                            int astr, int aoff, void* out, int ostr, int ooff, bool f32, hipStream_t s) {
   const int segs = B * H * cdiv(W, fh::PX);
-  const dim3 grid(cdiv(segs, 4));
+  if (segs <= 0) return;
   if (f32) {
     const float* ab = static_cast<const float*>(act);
     float* ob = static_cast<float*>(out);
     if (cin == 256)
-      hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<4, float>), grid, dim3(256), 0, s, dflow, w, B, H, W, ab, astr,
-                         aoff, ob, ostr, ooff);
+      hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<4, float>), dim3(fh::dgrad_grid<4, float>(segs)), dim3(256), 0, s,
+                         dflow, w, B, H, W, ab, astr, aoff, ob, ostr, ooff);
     else
-      hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<2, float>), grid, dim3(256), 0, s, dflow, w, B, H, W, ab, astr,
-                         aoff, ob, ostr, ooff);
+      hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<2, float>), dim3(fh::dgrad_grid<2, float>(segs)), dim3(256), 0, s,
+                         dflow, w, B, H, W, ab, astr, aoff, ob, ostr, ooff);
     return;
   }
   const bf16_t* ab = static_cast<const bf16_t*>(act);
   bf16_t* ob = static_cast<bf16_t*>(out);
   if (cin == 256)
-    hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<4, bf16_t>), grid, dim3(256), 0, s, dflow, w, B, H, W, ab, astr,
-                       aoff, ob, ostr, ooff);
+    hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<4, bf16_t>), dim3(fh::dgrad_grid<4, bf16_t>(segs)), dim3(256), 0, s,
+                       dflow, w, B, H, W, ab, astr, aoff, ob, ostr, ooff);
   else
-    hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<2, bf16_t>), grid, dim3(256), 0, s, dflow, w, B, H, W, ab, astr,
-                       aoff, ob, ostr, ooff);
+    hipLaunchKernelGGL((fh::flowhead_dgrad_kernel<2, bf16_t>), dim3(fh::dgrad_grid<2, bf16_t>(segs)), dim3(256), 0, s,
+                       dflow, w, B, H, W, ab, astr, aoff, ob, ostr, ooff);
 }
 
 }  // namespace rs

@@ -81,6 +81,8 @@ void flowhead_fwd_launch(const void* x, int xstr, int xoff, int cin, const float
                          int H, int W, float* crd, const float* src, bool x_f32, hipStream_t s);
 void flowhead_dgrad_launch(const float* dflow, const float* w, int cin, int B, int H, int W, const void* act,
                            int astr, int aoff, void* out, int ostr, int ooff, bool f32, hipStream_t s);
+void flowhead_set_dgrad_blocks(int n);
+int flowhead_dgrad_blocks();
 void gru_gate_bwd_launch(float* dh, int dhstr, const void* z, int zstr, const void* q, int qstr, const void* h,
                          int hstr, int hoff, void* dq, int dqstr, void* dzr, int dzrstr, long P, int hd, bool f32,
                          hipStream_t stream);
@@ -514,6 +516,10 @@ void flow_head_dgrad(const Tensor& dflow, const Tensor& w, int64_t cin, const Te
                             aoff, out.data_ptr(), out.size(3), ooff, f32, stream());
   RS_CHECK_LAUNCH();
 }
+
+// grid size of flow_head_dgrad's persistent kernel (RS_FH_BLOCKS, ops/_ext.py); 0: from the CU count
+void flow_head_set_dgrad_blocks(int64_t n) { rs::flowhead_set_dgrad_blocks((int)std::min<int64_t>(n, 1 << 20)); }
+int64_t flow_head_dgrad_blocks() { return rs::flowhead_dgrad_blocks(); }
 
 // dW (fp32, [>=Cout][taps][Ktot], accumulated) += sum_p dY[p][yoff + co] X[p + tap][k]
 // SY, SX > 1: a strided conv; the segments are on the INPUT grid (any Hi x Wi,
@@ -962,6 +968,8 @@ TORCH_LIBRARY_FRAGMENT(raft_stir, m) {
         "int KH, int KW, Tensor(a!) dw, Tensor(b!)? db=None, int bn128=0) -> ()");
   m.def("flow_head(Tensor x, int xoff, int cin, Tensor w, Tensor bias, Tensor(a!) crd, Tensor? src) -> ()");
   m.def("flow_head_dgrad(Tensor dflow, Tensor w, int cin, Tensor act, int aoff, Tensor(a!) out, int ooff) -> ()");
+  m.def("flow_head_set_dgrad_blocks(int n) -> ()", &flow_head_set_dgrad_blocks);
+  m.def("flow_head_dgrad_blocks() -> int", &flow_head_dgrad_blocks);
   m.def("colsum(Tensor dy, int yoff, int C, Tensor(a!) db) -> ()");
   m.def("flow_wgrad(Tensor coords, Tensor df, Tensor(a!) dw, Tensor(b!) db) -> ()");
   m.def("conv_wgrad_strided(Tensor dy, int Cout, Tensor[] segs, int[] seg_off, int[] seg_C, int KH, int KW, "

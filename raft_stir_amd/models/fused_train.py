@@ -16,19 +16,20 @@ into an [iters * B, H, W, C] slot instead of being overwritten:
   S.head, S.mask              flow-head/mask hidden (ReLU), convex mask
   S.C[i]                      coords before update i (iters + 1 slots)
 
-The convex upsampling of all iterations is one launch after the loop (the
-predictions do not feed back), so the Function returns one
-[iters * B, 2, 8H, 8W] tensor that the model splits into views; the fused
-sequence loss (train/loss.py) consumes it whole.
+The mask head's 1x1 conv and the convex upsampling of all iterations are one
+launch each after the loop (the predictions do not feed back), so the
+Function returns one [iters * B, 2, 8H, 8W] tensor that the model splits into
+views; the fused sequence loss (train/loss.py) consumes it whole.
 
 Weights are packed for the kernels by one static gather per step (and the
 gradients unpacked by one), see FusedTrainEngine._build_maps.
 
-Backward: one batched convex_upsample_backward, then iteration by iteration
+Backward: one batched convex_upsample_backward, the mask2 / flow dgrads
+(through the hidden ReLU) -> d head of every iteration in one launch each
+(_HEAD_BATCH: nothing in the loop feeds them), then iteration by iteration
 in reverse (dgrads = the forward conv kernel with transposed + flipped
 packed weights and gradient epilogues):
 
-  mask2 / flow dgrad (through the hidden ReLU)  -> d head
   head dgrad             -> dh  (fp32, accumulated with dh of iteration i+1)
   GRU pass 2, pass 1     -> gate backward kernel, q-conv dgrad with the
                             r-gate epilogue, zr-conv dgrad (fp32 accumulation
@@ -83,6 +84,13 @@ _SMALL_KPAD = os.environ.get("RS_SMALL_KPAD", "1") != "0"
 # lookup backward, ahead of the weight-gradient issue (ops/corr.py
 # CorrState.early_backward); RS_EARLY_CORR_BWD=0 leaves it to autograd
 _EARLY_CORR_BWD = os.environ.get("RS_EARLY_CORR_BWD", "1") != "0"
+# the kernels of the update loop that the recurrence does not wait for, issued
+# once per step over all iters * B images instead of once per iteration on the
+# serial chain: the mask head's 1x1 conv (only convex_upsample reads it, after
+# the loop), its input gradient and the flow head's (d_mask and dflow are
+# complete before the backward loop starts; coords are detached per iteration).
+# RS_HEAD_BATCH=0 keeps the per-iteration order (A/B, tests/test_head_batch_gpu.py)
+_HEAD_BATCH = os.environ.get("RS_HEAD_BATCH", "1") != "0"
 # fp32 engine: split fragment-major copies of the packed weights for the fp32
 # weight-streaming tiles (csrc/conv_v3f.hip), made per step after the gather
 _V3F_TRAIN = True
@@ -644,10 +652,14 @@ class FusedTrainLoop(torch.autograd.Function):
             conv_fused([(hx1, 0, HD)], eng.head.w, eng.head.b, 3, 3, 512, EPI_RELU, head, 0)
             # coords_{i+1} = coords_i + delta (out of place: the history is kept for backward)
             R.flow_head(head, 0, 256, eng.flow_w32, eng.flow.b, sl(C, i + 1), coords)
-            conv_fused([(head, 256, 256)], eng.mask2.w, eng.mask2.b, 1, 1, 576, EPI_SCALE, sl(S["mask"], i), 0,
-                       scale=0.25)
-        # every iteration's convex upsampling in one launch (they do not feed back)
+            if not _HEAD_BATCH:
+                conv_fused([(head, 256, 256)], eng.mask2.w, eng.mask2.b, 1, 1, 576, EPI_SCALE, sl(S["mask"], i), 0,
+                           scale=0.25)
+        # every iteration's mask conv and convex upsampling in one launch each (they do not feed back)
         n = iters * B
+        if _HEAD_BATCH:
+            conv_fused([(S["head"], 256, 256)], eng.mask2.w, eng.mask2.b, 1, 1, 576, EPI_SCALE, S["mask"], 0,
+                       scale=0.25, tune_batch=B)
         flows = (C[B:].view(iters, B, 2, H, W) - c0).view(n, 2, H, W)
         up = R.convex_upsample(flows, S["mask"])
         ctx.eng, ctx.state, ctx.S, ctx.iters = eng, corr_state, S, iters
@@ -692,11 +704,24 @@ class FusedTrainLoop(torch.autograd.Function):
         # the mask gradient straight into the padded d_mask slots (channels 576.. stay zero)
         dflow, _ = R.convex_upsample_backward(flows, S["mask"], g_up.contiguous(), S["d_mask"])
         S["d_flow"][..., :2].copy_(dflow.permute(0, 2, 3, 1))
+        if _HEAD_BATCH:
+            # d_head of every iteration before the loop: the flow head's half on the side
+            # stream, parallel to the mask head's (disjoint channels), joined here
+            if side is not None:
+                side.wait_stream(main)
+            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+                R.flow_head_dgrad(dflow, eng.flow_w32, 256, S["head"], 0, S["d_head"], 0)
+            conv_fused([(S["d_mask"], 0, 576)], eng.mask2.wd, None, 1, 1, 256, EPI_RELU_BWD, S["d_head"], 256,
+                       aux1=S["head"], a1off=256, tune_batch=B)
+            if side is not None:
+                main.wait_stream(side)
         for i in reversed(range(iters)):
             hx, hx1, head = sl(S["hx"], i), sl(S["hx"], i + 1), sl(S["head"], i)
             dm, df, dh = sl(S["d_mask"], i), sl(S["d_flow"], i), sl(S["d_head"], i)
-            conv_fused([(dm, 0, 576)], eng.mask2.wd, None, 1, 1, 256, EPI_RELU_BWD, dh, 256, aux1=head, a1off=256)
-            R.flow_head_dgrad(sl(dflow, i), eng.flow_w32, 256, head, 0, dh, 0)
+            if not _HEAD_BATCH:
+                conv_fused([(dm, 0, 576)], eng.mask2.wd, None, 1, 1, 256, EPI_RELU_BWD, dh, 256, aux1=head,
+                           a1off=256)
+                R.flow_head_dgrad(sl(dflow, i), eng.flow_w32, 256, head, 0, dh, 0)
             conv_fused([(dh, 0, 512)], eng.head.wd, None, 3, 3, HD, EPI_ACC_F32, G, 0)
             h_in = [(hx, 0), (sl(S["h1"], i), 0)]
             for p in (1, 0):
@@ -933,9 +958,12 @@ def _small_backward(ctx, g_up):
     dflow = torch.ops.raft_stir.upflow8_backward(g_up.float().contiguous(), ah, aw)
     S["d_flow"][..., :2].copy_(dflow.permute(0, 2, 3, 1))
     zr, q = eng.zr[0], eng.q[0]
+    if _HEAD_BATCH:  # d_head of every iteration in one launch (dflow is complete, coords are detached)
+        R.flow_head_dgrad(dflow, eng.flow_w32, 128, S["head"], 0, S["d_head"], 0)
     for i in reversed(range(iters)):
         hx, head, dh = sl(S["hx"], i), sl(S["head"], i), sl(S["d_head"], i)
-        R.flow_head_dgrad(sl(dflow, i), eng.flow_w32, 128, head, 0, dh, 0)
+        if not _HEAD_BATCH:
+            R.flow_head_dgrad(sl(dflow, i), eng.flow_w32, 128, head, 0, dh, 0)
         conv_fused([(dh, 0, 128)], eng.head.wd, None, 3, 3, hd, EPI_ACC_F32, G, 0)
         z, r, qq = sl(S["z"][0], i), sl(S["r"][0], i), sl(S["q"][0], i)
         dq, dzr = sl(S["d_q"][0], i), sl(S["d_zr"][0], i)

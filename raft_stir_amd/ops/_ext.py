@@ -47,6 +47,8 @@ def load(raise_on_error: bool = False) -> bool:
                     _LOADED = True
                     if os.environ.get("RS_NORM_REDUCE_BLOCKS"):  # in-situ A/B knob (csrc/norm.hip)
                         torch.ops.raft_stir.norm_set_reduce_blocks(int(os.environ["RS_NORM_REDUCE_BLOCKS"]))
+                    if os.environ.get("RS_FH_BLOCKS"):  # grid of the flow-head dgrad (csrc/flowhead.hip)
+                        torch.ops.raft_stir.flow_head_set_dgrad_blocks(int(os.environ["RS_FH_BLOCKS"]))
                 except Exception as e:  # pragma: no cover - depends on box
                     _LOADED, _ERROR = False, repr(e)
     if raise_on_error and not _LOADED:

@@ -237,12 +237,15 @@ def frag_eligible(w: torch.Tensor, kh: int, kw: int) -> bool:
 
 def conv_fused(segs: List[Tuple[torch.Tensor, int, int]], w, bias, kh, kw, cout, epi, out, ooff=0,
                scale=1.0, hd=0, out2=None, o2off=0, out3=None, o3off=0, aux1=None, a1off=0,
-               aux2=None, a2off=0, tile=None, nscale=None, wf=None):
+               aux2=None, a2off=0, tile=None, nscale=None, wf=None, tune_batch=None):
     """segs: list of (NHWC bf16 buffer, channel offset, channels read).
     ``nscale`` with ``epi=EPI_NORM``: out = [relu if hd](acc * nscale + bias)
     [then relu(. + aux1)].  ``wf``: the same weight in the fragment-major
     layout (:func:`frag_weight`), which the weight-streaming tiles 56-68 read;
-    without it those tiles are not chosen."""
+    without it those tiles are not chosen.  ``tune_batch``: the images of one
+    call when this call stacks several of them (every iteration of the update
+    loop): without a measured entry for the stacked shape the tile is the one
+    that call gets, so every element keeps its K order at any shape."""
     if wf is None:  # the training engine tags its packed weights with their fragment-major copy
         wf = getattr(w, "_rs_frag", None)
     tensors = [s[0] for s in segs]
@@ -251,11 +254,17 @@ def conv_fused(segs: List[Tuple[torch.Tensor, int, int]], w, bias, kh, kw, cout,
     if _RECORD is not None:
         _RECORD.append(dict(segs=segs, w=w, bias=bias, kh=kh, kw=kw, cout=cout, epi=epi, out=out, ooff=ooff,
                             scale=scale, hd=hd, out2=out2, o2off=o2off, out3=out3, o3off=o3off, aux1=aux1,
-                            a1off=a1off, aux2=aux2, a2off=a2off, tile=tile, nscale=nscale, wf=wf))
+                            a1off=a1off, aux2=aux2, a2off=a2off, tile=tile, nscale=nscale, wf=wf,
+                            tune_batch=tune_batch))
     if tile is None:
         t0 = tensors[0]
-        key = tune_key(t0.shape[0], t0.shape[1], t0.shape[2], cout, chans, kh, kw, epi)
-        P = t0.shape[0] * t0.shape[1] * t0.shape[2]
+        Bk = t0.shape[0]
+        key = tune_key(Bk, t0.shape[1], t0.shape[2], cout, chans, kh, kw, epi)
+        table = tuned_tiles_f32() if t0.dtype == torch.float32 else tuned_tiles()
+        if tune_batch and key not in table:
+            Bk = int(tune_batch)
+            key = tune_key(Bk, t0.shape[1], t0.shape[2], cout, chans, kh, kw, epi)
+        P = Bk * t0.shape[1] * t0.shape[2]
         if t0.dtype == torch.float32:  # split-bf16 F32 tiles: measured table, else the heuristic
             tile = tuned_tiles_f32().get(key)
             has32 = getattr(w, "_rs_frag32", None) is not None and all(c % 64 == 0 for c in chans)

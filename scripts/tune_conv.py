@@ -23,6 +23,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 F32_CANDIDATES = [6, 7, 8, 38, 39, 40, 81, 82, 83, 84, 85]
+STACKED = {}  # stacked call's key -> the key of its per-iteration call (record_calls)
 CANDIDATES = [3, 4, 6, 7, 16, 17, 19, 20, 21, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 42, 43,
               44, 45, 46, 48, 49, 50, 51, 52, 53, 54, 56, 57, 61, 65, 66, 68, 70]  # 56-68: calls that carry a wf weight; 70: 1x1
 
@@ -47,7 +48,13 @@ def record_calls(args):
             t0 = c["segs"][0][0]
             key = C.tune_key(t0.shape[0], t0.shape[1], t0.shape[2], c["cout"], [s[2] for s in c["segs"]],
                              c["kh"], c["kw"], c["epi"])
-            if c["tile"] is None and key not in calls:
+            if c.get("tune_batch"):
+                # a call over all iterations' images (models/fused_train.py _HEAD_BATCH) is not tuned on
+                # its own: it keeps the tile of the per-iteration call, so that every element keeps its K
+                # order whether the engine stacks the call or not (tests/test_head_batch_gpu.py)
+                STACKED[key] = C.tune_key(c["tune_batch"], t0.shape[1], t0.shape[2], c["cout"],
+                                          [s[2] for s in c["segs"]], c["kh"], c["kw"], c["epi"])
+            elif c["tile"] is None and key not in calls:
                 calls[key] = (tag, c)
         C._RECORD = None
 
@@ -159,6 +166,9 @@ def main():
         report.append(dict(key=key, phase=tag, heuristic=heur, us_heuristic=round(res.get(heur, res[best]), 2), best=best,
                            us_best=round(res[best], 2)))
         print(f"{tag:5s} {key:42s} heur t{heur} {res.get(heur, float('nan')):7.1f}us  best t{best} {res[best]:7.1f}us", flush=True)
+    for key, per_iteration in STACKED.items():
+        if per_iteration in table:
+            table[key] = table[per_iteration]
     section, rsection = ("tiles_f32", "report_f32") if args.f32 else ("tiles", "report")
     old = {}
     if os.path.exists(args.out):
