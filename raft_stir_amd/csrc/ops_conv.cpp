@@ -826,6 +826,9 @@ void relu_take(const Tensor& G, int64_t goff, int64_t n, int64_t nz, const Tenso
                   aoff + n <= act.size(-1),
               "relu_take: act (the out dtype)");
   TORCH_CHECK(out.is_contiguous() && out.scalar_type() == adt && n <= out.size(-1), "relu_take: out");
+  // the kernel walks out's channels: it zeroes G only as far as out is wide
+  TORCH_CHECK(n >= 0 && nz >= 0 && nz <= out.size(-1), "relu_take: nz (", nz, ") wider than out (", out.size(-1),
+              " channels): G[:, goff:goff+nz] cannot be zeroed");
   const c10::DeviceGuard guard(out.device());
   rs::relu_take_launch(G.data_ptr<float>(), G.size(-1), goff, n, nz, act.data_ptr(), act.size(-1), aoff, out.data_ptr(),
                        out.size(-1), P, f32, stream());
