@@ -14,7 +14,9 @@ asked for after the sequence has run (:meth:`DenseMultiFlowTracker.query`).
 The inverse map, which anchor pixel sits on every cell of frame t, comes from
 forward splatting (:meth:`DenseMultiFlowTracker.splat`, ops.forward_splat)
 and carries labels of the first frame through the video
-(:meth:`DenseMultiFlowTracker.warp_labels`); it is ATen on the CPU so far.
+(:meth:`DenseMultiFlowTracker.warp_labels`); on the GPU it is the scatter and
+resolve kernels of csrc/forward_splat.hip, an eager call after the step's
+replay, on the CPU the ATen oracle.
 """
 from __future__ import annotations
 
@@ -116,9 +118,11 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         inv_pos (1,2,H,W), the cell's position in the anchor frame, NaN at
         holes; out (1,C,H,W) fp32, ``values`` carried along and ``fill`` at
         holes, None without values).  On the first frame it is the identity:
-        every cell is covered by itself.  The tensors are the caller's own.
-        A tracker on the CPU only: there is no HIP kernel for the splat yet,
-        and on the GPU this raises NotImplementedError."""
+        every cell is covered by itself.  The tensors are the caller's own,
+        on the tracker's device.  On the GPU this is an eager call of
+        csrc/forward_splat.hip on the current stream, after the step's replay:
+        it reads the graph's static ``pos`` and ``score``, is not part of the
+        step graph and does not synchronise with the host."""
         from ..ops import forward_splat
         if self.pos is None:
             raise ValueError("splat() needs a step first")
@@ -133,8 +137,8 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         shape and dtype: at every cell the label of the anchor pixel that
         :meth:`splat` finds there, ``fill`` at holes; covered (1,1,H,W) bool).
         fp32 labels are gathered by the splat itself; every other dtype by one
-        gather along ``src_index``, so integer labels stay exact.  As
-        :meth:`splat`, on a CPU tracker only."""
+        gather along ``src_index``, so integer labels stay exact; both on the
+        tracker's device, as :meth:`splat`."""
         if self.pos is None:
             raise ValueError("warp_labels() needs a step first")
         H, W = self.pos.shape[-2:]

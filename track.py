@@ -41,7 +41,9 @@ from the dense field after every step (``DenseMultiFlowTracker.query``);
 
 ``--dense --labels mask.png [--splat_footprint {1,2}]`` carries a label image
 of the first frame (8- or 16-bit, one channel, the first frame's size) through
-the video by forward splatting (``ops.forward_splat``, computed on the host): per
+the video by forward splatting on the model's device (``ops.forward_splat``:
+csrc/forward_splat.hip on the GPU; only the warped labels and the coverage go
+to the host, to be written): per
 frame t ``labels_TTTT.png``, in the mask's bit depth with 0 where no pixel of
 the first frame lands, and ``covered_TTTT.png`` (255: some pixel lands there).
 The mask is padded like the frames, with label 0, and the images are cropped
@@ -63,7 +65,6 @@ from raft_stir_amd.data.frame_utils import writeFlow  # noqa: E402
 from raft_stir_amd.export.denseflow import DenseMultiFlowTracker  # noqa: E402
 from raft_stir_amd.export.multiflow import MultiFlowTracker  # noqa: E402
 from raft_stir_amd.export.pointtrack import SequenceTracker  # noqa: E402
-from raft_stir_amd.ops import forward_splat  # noqa: E402
 from raft_stir_amd.utils.padder import InputPadder  # noqa: E402
 
 
@@ -126,19 +127,17 @@ def track_dense(args, model, images, pts, dev):
         if mask.shape != (padder.ht, padder.wd):
             raise ValueError(f"{args.labels}: the first frame's size {(padder.ht, padder.wd)} expected, got "
                              f"{mask.shape}")
-        # the padding carries label 0, not a replicated border; the labels stay on the host
-        labels = torch.nn.functional.pad(torch.from_numpy(mask.astype(np.int32)), padder._pad, value=0)
+        # the padding carries label 0, not a replicated border
+        labels = torch.nn.functional.pad(torch.from_numpy(mask.astype(np.int32)), padder._pad, value=0).to(dev)
     cols = [[], [], [], [], []]
     for t, f in enumerate(images):
         tracker.step(padder.pad(load_image(f, dev))[0])
         if labels is not None:
-            # on the host, where the images are written anyway: forward splatting has no HIP kernel yet
-            src, covered, _, _ = forward_splat(tracker.pos.cpu(), tracker.score.cpu(), footprint=args.splat_footprint)
-            warped = labels.reshape(-1)[src[0, 0].long().clamp(min=0)]
-            warped = torch.where(covered[0, 0], warped, torch.zeros_like(warped))
-            warped = padder.unpad(warped).numpy().astype(mask.dtype)
+            # splatted where the field is; only what is written goes to the host
+            warped, covered = tracker.warp_labels(labels, footprint=args.splat_footprint, fill=0)
+            warped = padder.unpad(warped).cpu().numpy().astype(mask.dtype)
             Image.fromarray(warped).save(os.path.join(args.out, f"labels_{t:04d}.png"))
-            covered = padder.unpad(covered)[0, 0].numpy()
+            covered = padder.unpad(covered)[0, 0].cpu().numpy()
             Image.fromarray(covered.astype(np.uint8) * 255).save(os.path.join(args.out, f"covered_{t:04d}.png"))
         # a difference of two positions: the padding's shift cancels
         flow = padder.unpad(tracker.flow)[0].permute(1, 2, 0).cpu().numpy()
