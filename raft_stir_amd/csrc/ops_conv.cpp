@@ -114,6 +114,7 @@ bool deterministic();
 bool enc_halo_launch(const uint16_t* x, int xstr, const uint16_t* w, int Ktot, uint16_t* y, int ystr, int B, int H,
                      int W, int cin, int cout, int num_cus, const EncEpi& e, hipStream_t stream);
 bool enc_halo_supported(int cin, int cout);
+void enc_halo_set_pipe(int on);
 struct StemLaunch {  // must match stem.hip
   const void* x;
   int x_bf16, B, Hi, Wi, Ho, Wo;
@@ -894,6 +895,9 @@ void conv3x3_halo(const Tensor& x, const Tensor& w, const Tensor& y, int64_t cin
   RS_CHECK_LAUNCH();
 }
 
+// Tile loop of the halo kernel: 1 pipelined, 0 the plain loop, < 0 what RS_HALO_PIPE set at load (A/B, tests).
+void conv3x3_halo_set_pipe(int64_t on) { rs::enc_halo_set_pipe((int)on); }
+
 // 7x7 / stride-2 / pad-3 stem conv, 3 -> Cout <= 64 (csrc/stem.hip).
 //   x: NHWC image [B, Hi, Wi, 3] fp32 or bf16; w: packed [64][7][32] bf16 (k = kx*3 + ci;
 //   fp32 output: the split [64][7][64] layout); out: NHWC [B, Ho, Wo, >= Cout] (bf16, or
@@ -967,6 +971,7 @@ TORCH_LIBRARY_FRAGMENT(raft_stir, m) {
   m.def("conv3x3_halo(Tensor x, Tensor w, Tensor(a!) y, int cin, int cout, "
         "Tensor? nscale=None, Tensor? nshift=None, Tensor? res=None, "
         "bool relu=False, bool accumulate=False) -> ()");
+  m.def("conv3x3_halo_set_pipe(int on) -> ()", &conv3x3_halo_set_pipe);
   m.def("conv_wgrad(Tensor dy, int yoff, int Cout, Tensor[] segs, int[] seg_off, int[] seg_C, int[] seg_period, "
         "int KH, int KW, Tensor(a!) dw, Tensor(b!)? db=None, int bn128=0) -> ()");
   m.def("flow_head(Tensor x, int xoff, int cin, Tensor w, Tensor bias, Tensor(a!) crd, Tensor? src) -> ()");
