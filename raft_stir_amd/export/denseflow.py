@@ -16,7 +16,9 @@ forward splatting (:meth:`DenseMultiFlowTracker.splat`, ops.forward_splat)
 and carries labels of the first frame through the video
 (:meth:`DenseMultiFlowTracker.warp_labels`); on the GPU it is the scatter and
 resolve kernels of csrc/forward_splat.hip, an eager call after the step's
-replay, on the CPU the ATen oracle.
+replay, on the CPU the ATen oracle.  The holes the splat leaves where the
+scene stretches can be filled from the nearest covered cell within a radius
+(``inpaint=R`` of the three methods, ops.splat_inpaint, csrc/splat_inpaint.hip).
 """
 from __future__ import annotations
 
@@ -110,7 +112,7 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         return reference.dense_query(self.pos, self.score, points.to(self.pos.device, torch.float32))
 
     @torch.no_grad()
-    def splat(self, values=None, footprint: int = 2, fill: float = 0.0):
+    def splat(self, values=None, footprint: int = 2, fill: float = 0.0, inpaint: int | None = 0):
         """The inverse map of the current frame, by forward splatting
         (ops.forward_splat on ``pos`` and ``score``): for every cell of frame
         t the anchor pixel that sits there.  values (1,C,H,W) or None ->
@@ -122,23 +124,38 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         on the tracker's device.  On the GPU this is an eager call of
         csrc/forward_splat.hip on the current stream, after the step's replay:
         it reads the graph's static ``pos`` and ``score``, is not part of the
-        step graph and does not synchronise with the host."""
-        from ..ops import forward_splat
+        step graph and does not synchronise with the host.
+
+        ``inpaint`` = R > 0 (None: unlimited) fills every hole that has a
+        covered cell within R cells from the nearest one (ops.splat_inpaint,
+        csrc/splat_inpaint.hip on the GPU, right after the splat on the same
+        stream): ``src_index``, ``inv_pos`` and ``out`` are the in-painted
+        ones, ``covered`` stays the true coverage, so
+        ``(src_index >= 0) & ~covered`` marks the in-painted cells.  With the
+        default 0 the op is not called."""
+        from ..ops import forward_splat, splat_inpaint
         if self.pos is None:
             raise ValueError("splat() needs a step first")
         if values is not None:
             values = values.to(self.pos.device)
-        return forward_splat(self.pos, self.score, values, footprint=footprint, fill=fill)
+        if inpaint == 0:  # None is unlimited, not 0
+            return forward_splat(self.pos, self.score, values, footprint=footprint, fill=fill)
+        src, covered, inv, _ = forward_splat(self.pos, self.score, None, footprint=footprint)
+        src, _, _, inv, out = splat_inpaint(src, self.pos, inv, values, max_dist=inpaint, fill=fill)
+        return src, covered, inv, out
 
     @torch.no_grad()
-    def warp_labels(self, labels, footprint: int = 2, fill=0):
+    def warp_labels(self, labels, footprint: int = 2, fill=0, inpaint: int | None = 0):
         """Carry labels of the anchor frame into the current frame.  labels
         (H,W), (1,1,H,W) or (1,C,H,W), of any dtype -> (warped, of labels'
         shape and dtype: at every cell the label of the anchor pixel that
         :meth:`splat` finds there, ``fill`` at holes; covered (1,1,H,W) bool).
         fp32 labels are gathered by the splat itself; every other dtype by one
         gather along ``src_index``, so integer labels stay exact; both on the
-        tracker's device, as :meth:`splat`."""
+        tracker's device, as :meth:`splat`.  With ``inpaint`` = R > 0 (None:
+        unlimited) holes within R cells of a covered cell take that cell's
+        label, as :meth:`splat` describes; ``covered`` is the true coverage
+        all the same."""
         if self.pos is None:
             raise ValueError("warp_labels() needs a step first")
         H, W = self.pos.shape[-2:]
@@ -147,20 +164,21 @@ class DenseMultiFlowTracker(MultiFlowTracker):
             raise ValueError(f"labels must be (H,W), (1,1,H,W) or (1,C,H,W) with H, W = {(H, W)}, got {shape}")
         lab = labels.to(self.pos.device).reshape(1, -1, H, W)
         if lab.dtype == torch.float32:
-            _, covered, _, out = self.splat(lab, footprint=footprint, fill=float(fill))
+            _, covered, _, out = self.splat(lab, footprint=footprint, fill=float(fill), inpaint=inpaint)
             return out.reshape(shape), covered
-        src, covered, _, _ = self.splat(None, footprint=footprint)
+        src, covered, _, _ = self.splat(None, footprint=footprint, inpaint=inpaint)
         got = lab.reshape(-1, H * W).index_select(1, src.reshape(-1).long().clamp_(min=0)).reshape(1, -1, H, W)
         hole = torch.full((), fill, dtype=lab.dtype, device=lab.device)
-        return torch.where(covered, got, hole).reshape(shape), covered
+        return torch.where(covered if inpaint == 0 else src >= 0, got, hole).reshape(shape), covered
 
     @torch.no_grad()
-    def track(self, frames, labels=None, footprint: int = 2, fill=0):
+    def track(self, frames, labels=None, footprint: int = 2, fill=0, inpaint: int | None = 0):
         """frames (T,1,3,H,W) or a list of (1,3,H,W) -> (flows (T,2,H,W), the
         long-term flow 0 -> t of every pixel, visible (T,1,H,W) bool);
         ``flows[0] == 0``.  With ``labels`` of the first frame
-        (:meth:`warp_labels`) two more: the labels warped into every frame,
-        (T,) + labels.shape, and covered (T,1,H,W) bool."""
+        (:meth:`warp_labels`, which takes ``inpaint``) two more: the labels
+        warped into every frame, (T,) + labels.shape, and covered (T,1,H,W)
+        bool."""
         if len(frames) < 1:
             raise ValueError("track() needs at least one frame")
         self.reset()
@@ -170,7 +188,7 @@ class DenseMultiFlowTracker(MultiFlowTracker):
             flows.append(self.flow[0])
             vis.append(self.visible[0].clone())
             if labels is not None:
-                w, c = self.warp_labels(labels, footprint=footprint, fill=fill)
+                w, c = self.warp_labels(labels, footprint=footprint, fill=fill, inpaint=inpaint)
                 warped.append(w)
                 cov.append(c[0])
         if labels is None:

@@ -492,3 +492,111 @@ def forward_splat(pos, score, values=None, footprint: int = 2, fill: float = 0.0
         v = values.float().reshape(-1, N)
         out = torch.where(covered, v[:, win], torch.full_like(v[:, :1], fill)).reshape(1, -1, H, W)
     return src_index.reshape(1, 1, H, W), covered.reshape(1, 1, H, W), inv.reshape(1, 2, H, W), out
+
+
+_INPAINT_NONE = torch.iinfo(torch.int64).max
+INPAINT_MAX_SIDE = 32767
+
+
+def _shift(t, d, axis, pad):
+    """s with s[i] = t[i - d] along ``axis`` of a 2-d tensor, ``pad`` where i - d is outside."""
+    out = torch.full_like(t, pad)
+    n = t.shape[axis]
+    if abs(d) >= n:
+        return out
+    src = slice(0, n - d) if d >= 0 else slice(-d, n)
+    dst = slice(d, n) if d >= 0 else slice(0, n + d)
+    if axis == 0:
+        out[dst] = t[src]
+    else:
+        out[:, dst] = t[:, src]
+    return out
+
+
+def splat_inpaint(src_index, pos, inv_pos, values=None, max_dist: int = 8, fill: float = 0.0):
+    """In-paint the holes of a forward splat from the nearest covered cell.
+    This docstring is the rule.  src_index (1,1,H,W) int32 and inv_pos
+    (1,2,H,W) as :func:`forward_splat` returns them; pos (1,2,H,W), the field
+    that was splatted; values (1,C,H,W) or None; max_dist R, an integer in
+    [0, 32767]; H, W in [2, 32767], so that every d2 and H*W stay below 2^31.
+
+    An entry s of src_index is read as ``clamp(s, -1, N-1)``, N = H*W: below 0
+    a hole, N and above the last anchor pixel.  A cell c = y*W + x is covered
+    iff ``s[c] >= 0``.  Every cell takes as donor the covered cell c' of
+    smallest key ``(d2 << 31) | c'`` with ``d2 = (x-x')^2 + (y-y')^2``: the
+    nearest covered cell in exact integer Euclidean distance, among equals the
+    lowest cell index.  The donor counts only if ``d2 <= R*R``.  A covered cell
+    is its own donor (d2 = 0); a hole without a covered cell within R stays a
+    hole.  With R = 0 the input comes back unchanged.
+
+    -> (src_index (1,1,H,W) int32: ``s[donor]``, -1 where there is none; donor
+    (1,1,H,W) int32: the donor's cell index, or -1; dist2 (1,1,H,W) int32: its
+    d2, or -1; inv_pos (1,2,H,W) fp32: at covered cells the input's value bit
+    for bit, at filled cells ``grid(win) + (cell - pos[win])`` per axis with
+    ``win = s[donor]`` (the donor's anchor pixel extended rigidly to this cell,
+    the two fp32 operations of splat::inverse in csrc/splat_device.h), NaN where
+    there is none; out (1,C,H,W) fp32: ``values[:, win]``, ``fill`` where there
+    is none, None without values).
+
+    The search is separable and exact.  Column pass: per cell the nearest
+    covered row y' of its own column with |y - y'| <= R, y - d before y + d
+    (the lower cell index), -1 if none.  Row pass: the donor of (x, y) is the
+    smallest key over x' in [x-R, x+R] of column x''s row at y, with d2 <= R*R.
+    A column's nearest row minimises d2 for every x and its tie went to the
+    lower index, so the minimum over the columns' keys is the minimum over all
+    covered cells.  Everything is integers but inverse's two fp32 operations,
+    and nothing depends on a visiting order.  O(R) whole-tensor shifts on int64
+    keys; no host synchronisation."""
+    _, _, H, W = src_index.shape
+    R = int(max_dist)
+    if not (2 <= H <= INPAINT_MAX_SIDE and 2 <= W <= INPAINT_MAX_SIDE):
+        raise ValueError(f"splat_inpaint: H, W in [2, {INPAINT_MAX_SIDE}] expected, got {(H, W)}")
+    if not 0 <= R <= INPAINT_MAX_SIDE:
+        raise ValueError(f"splat_inpaint: max_dist must be in [0, {INPAINT_MAX_SIDE}], got {max_dist}")
+    N, dev = H * W, src_index.device
+    s = src_index.reshape(H, W).long().clamp(-1, N - 1)
+    cov = s >= 0
+    ys = torch.arange(H, device=dev).view(H, 1).expand(H, W)
+    xs = torch.arange(W, device=dev).view(1, W).expand(H, W)
+    # column pass: the first hit in the order y, y-1, y+1, y-2, ...
+    col = torch.where(cov, ys, torch.full_like(ys, -1))
+    for d in range(1, min(R, H - 1) + 1):
+        for sign in (1, -1):  # sign = 1: the row y - d
+            hit = _shift(cov, sign * d, 0, False) & (col < 0)
+            col = torch.where(hit, ys - sign * d, col)
+    # row pass
+    none = torch.full((H, W), _INPAINT_NONE, dtype=torch.int64, device=dev)
+    best = none.clone()
+    for dx in range(0, min(R, W - 1) + 1):
+        for sign in ((1, -1) if dx else (1,)):  # sign = 1: the column x - dx
+            yc = _shift(col, sign * dx, 1, -1)
+            dy = ys - yc
+            d2 = dx * dx + dy * dy
+            key = (d2 << 31) | (yc * W + (xs - sign * dx))
+            best = torch.minimum(best, torch.where((yc >= 0) & (d2 <= R * R), key, none))
+    has = best != _INPAINT_NONE
+    zero = torch.zeros_like(best)
+    donor = torch.where(has, best & (2 ** 31 - 1), zero).reshape(N)
+    dist2 = torch.where(has, best >> 31, zero - 1).reshape(N)
+    has = has.reshape(N)
+    win = s.reshape(N)[donor]  # >= 0 where has: a donor is covered
+    win = torch.where(has, win, zero.reshape(N))
+    src_out = torch.where(has, win, torch.full_like(win, -1)).to(torch.int32)
+    n = torch.arange(N, device=dev)
+    cy = torch.div(n, W, rounding_mode="floor")
+    gx, gy = (n - cy * W).float(), cy.float()
+    wy = torch.div(win, W, rounding_mode="floor")
+    wx = win - wy * W
+    x, y = pos[0, 0].reshape(N).float(), pos[0, 1].reshape(N).float()
+    nan = torch.full_like(x, float("nan"))
+    own = cov.reshape(N)
+    given = inv_pos.reshape(2, N).float()
+    inv = torch.stack([torch.where(own, given[0], torch.where(has, wx.float() + (gx - x[win]), nan)),
+                       torch.where(own, given[1], torch.where(has, wy.float() + (gy - y[win]), nan))])
+    out = None
+    if values is not None:
+        v = values.float().reshape(-1, N)
+        out = torch.where(has, v[:, win], torch.full_like(v[:, :1], fill)).reshape(1, -1, H, W)
+    donor = torch.where(has, donor, torch.full_like(donor, -1)).to(torch.int32)
+    return (src_out.reshape(1, 1, H, W), donor.reshape(1, 1, H, W), dist2.to(torch.int32).reshape(1, 1, H, W),
+            inv.reshape(1, 2, H, W), out)

@@ -5,7 +5,7 @@ whole sequence, with RAFT's video warm start).
     python track.py --model M [--small --mixed_precision --iters 12 --no_warm_start] \
         [--fb_check [--fb_alpha A1 A2]] [--deltas 1 4 16 inf] [--cache_features] \
         --path demo-frames --points points.txt --out tracks.csv
-    python track.py --model M --dense --deltas 1 4 16 inf [--points points.txt] [--labels mask.png] \
+    python track.py --model M --dense --deltas 1 4 16 inf [--points points.txt] [--labels mask.png [--inpaint R]] \
         --path demo-frames --out tracks/
 
 ``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
@@ -47,7 +47,11 @@ to the host, to be written): per
 frame t ``labels_TTTT.png``, in the mask's bit depth with 0 where no pixel of
 the first frame lands, and ``covered_TTTT.png`` (255: some pixel lands there).
 The mask is padded like the frames, with label 0, and the images are cropped
-back.
+back.  ``--inpaint R`` (an integer or ``inf``; default 0: off) fills the holes
+that have a covered cell within R cells with that cell's label
+(``ops.splat_inpaint``: csrc/splat_inpaint.hip on the GPU);
+``covered_TTTT.png`` then holds 255 where a pixel lands, 128 where the label
+was in-painted and 0 at the holes that are left.
 """
 import argparse
 import csv
@@ -76,6 +80,16 @@ def _deltas(words):
         else:
             out.append(int(w))
     return tuple(out)
+
+
+def _radius(word):
+    """--inpaint: a radius in cells, or 'inf' for no limit (None)."""
+    if word.lower() in ("inf", "none"):
+        return None
+    r = int(word)
+    if not 0 <= r <= 32767:
+        raise argparse.ArgumentTypeError(f"a radius in [0, 32767] or 'inf' expected, got {word}")
+    return r
 
 
 def track_multi(args, model, images, pts, dev):
@@ -134,11 +148,19 @@ def track_dense(args, model, images, pts, dev):
         tracker.step(padder.pad(load_image(f, dev))[0])
         if labels is not None:
             # splatted where the field is; only what is written goes to the host
-            warped, covered = tracker.warp_labels(labels, footprint=args.splat_footprint, fill=0)
+            if args.inpaint == 0:
+                warped, covered = tracker.warp_labels(labels, footprint=args.splat_footprint, fill=0)
+                level = padder.unpad(covered)[0, 0].cpu().numpy().astype(np.uint8) * 255
+            else:
+                # the labels are integers: one gather along the in-painted map, which also tells filled from hole
+                src, covered, _, _ = tracker.splat(None, footprint=args.splat_footprint, inpaint=args.inpaint)
+                warped = labels.reshape(-1)[src.reshape(-1).long().clamp_(min=0)].reshape(labels.shape)
+                warped = torch.where(src[0, 0] >= 0, warped, torch.zeros_like(warped))
+                level = torch.where(covered, 255, torch.where(src >= 0, 128, 0)).to(torch.uint8)
+                level = padder.unpad(level)[0, 0].cpu().numpy()
             warped = padder.unpad(warped).cpu().numpy().astype(mask.dtype)
             Image.fromarray(warped).save(os.path.join(args.out, f"labels_{t:04d}.png"))
-            covered = padder.unpad(covered)[0, 0].cpu().numpy()
-            Image.fromarray(covered.astype(np.uint8) * 255).save(os.path.join(args.out, f"covered_{t:04d}.png"))
+            Image.fromarray(level).save(os.path.join(args.out, f"covered_{t:04d}.png"))
         # a difference of two positions: the padding's shift cancels
         flow = padder.unpad(tracker.flow)[0].permute(1, 2, 0).cpu().numpy()
         vis = padder.unpad(tracker.visible)[0, 0].cpu().numpy()
@@ -235,11 +257,16 @@ def parse_args(argv=None):
                              "frame's labels_TTTT.png and covered_TTTT.png go into the directory --out")
     parser.add_argument("--splat_footprint", type=int, choices=(1, 2), default=2,
                         help="with --labels: a pixel claims its nearest cell (1) or every cell it touches (2)")
+    parser.add_argument("--inpaint", type=_radius, default=0, metavar="R",
+                        help="with --labels: fill holes from the nearest covered cell within R cells (an integer, or "
+                             "'inf'); covered_TTTT.png then marks in-painted cells with 128")
     args = parser.parse_args(argv)
     if args.dense and not args.deltas:
         parser.error("--dense needs --deltas")
     if args.labels and not args.dense:
         parser.error("--labels needs --dense")
+    if args.inpaint != 0 and not args.labels:
+        parser.error("--inpaint needs --labels")
     if not args.dense and not args.points:
         parser.error("the following arguments are required: --points")
     return args
