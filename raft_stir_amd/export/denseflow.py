@@ -19,6 +19,11 @@ resolve kernels of csrc/forward_splat.hip, an eager call after the step's
 replay, on the CPU the ATen oracle.  The holes the splat leaves where the
 scene stretches can be filled from the nearest covered cell within a radius
 (``inpaint=R`` of the three methods, ops.splat_inpaint, csrc/splat_inpaint.hip).
+On a long sequence the tracker can be re-anchored on the current frame
+(:meth:`DenseMultiFlowTracker.reanchor`): the field so far is kept as a base and
+every later field is composed with it (ops.dense_compose,
+csrc/dense_compose.hip), so everything published stays indexed by the pixels of
+the first frame.
 """
 from __future__ import annotations
 
@@ -68,18 +73,58 @@ class DenseMultiFlowTracker(MultiFlowTracker):
     ``active`` row when it changes and the init (without ``cache_features``
     also its image copy per finite slot), and no copy per slot of dense
     state.  On a CPU model the same step runs eagerly on the ATen oracle.
+
+    Re-anchoring.  When most of the first frame has left the view, the pair
+    ``anchor -> t`` is the hardest of the step and finally useless.
+    :meth:`reanchor`, called after a step on frame r, keeps the published field
+    ``0 -> r`` as a base and restarts the sequence with frame r as the anchor.
+    From then on a step is the same graph, which now yields the inner field
+    ``r -> t``, followed by one eager ``ops.dense_compose(base_pos, base_score,
+    pos, score, delta, fb_err, out=...)`` on the same stream, and ``pos``,
+    ``score``, ``visible``, ``delta`` and ``fb_err`` are the composed ones,
+    ``0 -> t`` indexed by the pixels of frame 0 (static buffers of their own,
+    valid until the next step), so ``flow``, :meth:`splat`,
+    :meth:`warp_labels`, :meth:`query` and :meth:`track` work unchanged.  The
+    inner field is ``anchor_pos``, ``anchor_score`` and ``anchor_visible``,
+    indexed by the pixels of the current anchor, whose absolute frame index is
+    ``anchor_frame``; ``cand_err`` stays the inner field's, indexed by the
+    pixels of the current anchor.  Without a re-anchor the ``anchor_*``
+    attributes are ``pos``, ``score`` and ``visible`` themselves, the op is
+    never called, and bits, launches and published tensors are those of a
+    tracker without the feature.  Re-anchors chain: the base becomes the
+    composed field each time.  ``reanchor_every=N`` re-anchors after
+    publishing the N-th frame past the current anchor, without a host
+    synchronisation; ``reanchor_below=f``, 0 < f < 1, after publishing a frame
+    on which fewer than f of the current anchor's pixels are visible
+    (``anchor_visible``), which reads one scalar from the device per step: it
+    is the one option that synchronises with the host.  The price: a pixel
+    that is not visible on the re-anchor frame is lost for the rest of the
+    sequence (its base score is +inf, and the old anchor slot that could have
+    found it again is gone), the first step after a re-anchor starts cold, and
+    positions pass through one more bilinear interpolation per re-anchor.
     """
 
     def __init__(self, model, iters: int = NUMITERS, deltas=(1, 2, 4, 8, None), fb_alpha=(0.01, 0.5),
-                 warm_start: bool = True, cache_features: bool = False, cand_err: bool = False):
+                 warm_start: bool = True, cache_features: bool = False, cand_err: bool = False,
+                 reanchor_every: int | None = None, reanchor_below: float | None = None):
         self.want_cand_err = bool(cand_err)
+        if reanchor_every is not None and (isinstance(reanchor_every, bool) or not isinstance(reanchor_every, int)
+                                           or reanchor_every < 1):
+            raise ValueError(f"reanchor_every must be a positive int or None, got {reanchor_every!r}")
+        if reanchor_below is not None and not 0.0 < float(reanchor_below) < 1.0:
+            raise ValueError(f"reanchor_below must be in (0, 1) or None, got {reanchor_below!r}")
+        self.reanchor_every = reanchor_every
+        self.reanchor_below = None if reanchor_below is None else float(reanchor_below)
         super().__init__(model, iters=iters, deltas=deltas, fb_alpha=fb_alpha, warm_start=warm_start,
                          cache_features=cache_features)
 
     def reset(self):
-        """Forget the frames, the tracked field and the inits."""
+        """Forget the frames, the tracked field, the base of a re-anchor and the inits."""
         super().reset()
         self.pos = None
+        self.anchor_pos = self.anchor_score = self.anchor_visible = None
+        self.anchor_frame = 0
+        self._based = False   # a base field is held: the published field is composed with it
 
     # ------------------------------------------------------------------ public
     _needs_points = False
@@ -89,7 +134,62 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         if points is not None:
             raise ValueError("DenseMultiFlowTracker tracks every pixel: step() takes no points "
                              "(ask for them with query())")
-        return super().step(frame)
+        super().step(frame)
+        since = self.t - 1  # frames past the current anchor
+        if since >= 1 and ((self.reanchor_every is not None and since >= self.reanchor_every)
+                           or (self.reanchor_below is not None  # one scalar from the device: synchronises
+                               and float(self.anchor_visible.float().mean()) < self.reanchor_below)):
+            self.reanchor()
+        return self.pos
+
+    @torch.no_grad()
+    def reanchor(self):
+        """Make the current frame the anchor.  Valid after a step; before the
+        first advance of a sequence (or right after a re-anchor) it does
+        nothing.  The published ``pos`` and ``score`` are copied into the
+        tracker's base buffers (one set per frame shape) and the sequence
+        restarts on the current frame, which is still in the static frame
+        buffer, through the first-frame path (one re-encode with
+        ``cache_features``): the frame becomes the anchor in the feature or
+        image ring and in the state ring, ``t`` counts from it, every init is
+        zero and the finite slots become active again as frames arrive.  What
+        is published for this frame stays what it was (the composition through
+        the identity is not taken: a bilinear sample of the grid is not
+        bit-equal to the point); from the next step on it is the composed
+        field.  ``anchor_pos``, ``anchor_score`` and ``anchor_visible`` become
+        the identity field of the new anchor.  No host synchronisation."""
+        if self.t <= 1:
+            return
+        st = self._st
+        dev = st["grid"].device
+        H, W = st["grid"].shape[-2:]
+        if "base_pos" not in st:
+            st["base_pos"] = torch.empty(1, 2, H, W, device=dev)
+            st["base_score"] = torch.empty(1, 1, H, W, device=dev)
+            st["composed"] = (torch.empty(1, 2, H, W, device=dev), torch.empty(1, 1, H, W, device=dev),
+                              torch.empty(1, 1, H, W, dtype=torch.bool, device=dev),
+                              torch.empty(1, 1, H, W, dtype=torch.int32, device=dev),
+                              torch.empty(1, 1, H, W, device=dev))
+        st["base_pos"].copy_(self.pos)
+        st["base_score"].copy_(self.score)
+        if self._based:
+            # what is published lives in the buffers the next composition writes: keep this frame's own
+            self.pos, self.score, self.visible = self.pos.clone(), self.score.clone(), self.visible.clone()
+            self.delta, self.fb_err = self.delta.clone(), self.fb_err.clone()
+        if st["graph0"] is not None:
+            st["graph0"].replay()
+        else:
+            self._run_first(st)
+        self._seed(st)
+        self.anchor_frame += self.t - 1
+        self.t = 1
+        self._active_row = None  # the active table starts from row 1 again
+        self._next = st["zero"]
+        self.next_init = self._next
+        self._based = True
+        self.anchor_pos = st["grid"].clone()
+        self.anchor_score = torch.zeros(1, 1, H, W, device=dev)
+        self.anchor_visible = torch.ones(1, 1, H, W, dtype=torch.bool, device=dev)
 
     @property
     def flow(self):
@@ -102,14 +202,15 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         (positions (1,N,2) in the current frame, visible (1,N) bool, score
         (1,N)): the bilinear sample of ``pos`` at the points, visible iff every
         pixel it is read from is, the score the worst of theirs
-        (ops.reference.dense_query).  A point outside the anchor frame or
-        non-finite comes back unchanged, not visible, with score +inf."""
-        from ..ops import reference
+        (ops.dense_query: csrc/dense_compose.hip on the GPU, the ATen oracle on
+        the CPU).  A point outside the anchor frame or non-finite comes back
+        unchanged, not visible, with score +inf."""
+        from ..ops import dense_query
         if self.pos is None:
             raise ValueError("query() needs a step first")
         if points.dim() != 3 or points.shape[0] != 1 or points.shape[2] != 2:
             raise ValueError(f"points must be (1,N,2), got {tuple(points.shape)}")
-        return reference.dense_query(self.pos, self.score, points.to(self.pos.device, torch.float32))
+        return dense_query(self.pos, self.score, points.to(self.pos.device, torch.float32))
 
     @torch.no_grad()
     def splat(self, values=None, footprint: int = 2, fill: float = 0.0, inpaint: int | None = 0):
@@ -218,18 +319,32 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         """The state of a sequence's first frame: the grid, score 0, in row 0
         (which the inactive slots name too) and in the anchor's row."""
         H, W = frame.shape[-2:]
-        for row in (0, self.L + 1):
-            st["ring_pos"][row].copy_(st["grid"][0])
-            st["ring_score"][row].zero_()
+        self._seed(st)
         self.pos = st["grid"].clone()
         self.visible = torch.ones(1, 1, H, W, dtype=torch.bool, device=dev)
         self.score = torch.zeros(1, 1, H, W, device=dev)
         self.fb_err = torch.zeros(1, 1, H, W, device=dev)
         self.delta = torch.zeros(1, 1, H, W, dtype=torch.int32, device=dev)
+        self.anchor_pos, self.anchor_score, self.anchor_visible = self.pos, self.score, self.visible
         return self.pos
 
+    def _seed(self, st):
+        """The anchor's state: the grid with score 0 in row 0 and in the anchor's row of the state ring."""
+        for row in (0, self.L + 1):
+            st["ring_pos"][row].copy_(st["grid"][0])
+            st["ring_score"][row].zero_()
+
     def _publish(self, pos, score, vis, delta, err, cand):
-        """The attributes that describe the new frame: the graph's outputs themselves."""
+        """The attributes that describe the new frame: the graph's outputs
+        themselves, or after a re-anchor their composition with the base."""
+        self.anchor_pos, self.anchor_score, self.anchor_visible = pos, score, vis
+        self.cand_err = cand
+        if self._based:
+            from ..ops import dense_compose
+            st = self._st
+            # on the GPU into static buffers, as the graph's outputs are; on the CPU every step has its own tensors
+            pos, score, vis, delta, err = dense_compose(st["base_pos"], st["base_score"], pos, score, delta, err,
+                                                        out=st["composed"] if pos.is_cuda else None)
         self.pos, self.score, self.visible = pos, score, vis
-        self.delta, self.fb_err, self.cand_err = delta, err, cand
+        self.delta, self.fb_err = delta, err
         return self.pos

@@ -421,6 +421,42 @@ def dense_query(pos, score, points):
     return out, worst < inf, worst
 
 
+def dense_compose(base_pos, base_score, pos, score, delta, fb_err):
+    """Compose two dense track fields: ``base`` maps anchor a -> frame r, the
+    inner field (``pos``, ``score``, ``delta``, ``fb_err``, as
+    DenseMultiFlowTracker publishes them) maps r -> t; the result maps a -> t,
+    indexed by the pixels of a.  This docstring is the rule.  base_pos, pos
+    (1,2,H,W); base_score, score, fb_err (1,1,H,W); delta (1,1,H,W) int32.
+
+    With ``p, q_vis, q_score = dense_query(pos, score, base_pos as points)``:
+    ``pos_c = p`` (a base position outside the inner frame or non-finite comes
+    back unchanged); ``s = base_score + q_score`` (scores add as the tracker's
+    do: start score + fb_err); ``visible_c = q_vis & (s < +inf)`` (NaN fails,
+    -inf + inf fails); ``score_c = s`` where visible, else +inf, so that a
+    stored score is finite iff the pixel is visible; ``delta_c`` and
+    ``fb_err_c`` are the inner ``delta`` and ``fb_err`` at the pixel
+    ``(round x, round y)`` of the base position, halves to even (the splat's
+    class-0 cell), where visible, else -1 and +inf.
+    -> (pos_c (1,2,H,W), score_c (1,1,H,W), visible_c (1,1,H,W) bool, delta_c
+    (1,1,H,W) int32, fb_err_c (1,1,H,W)).  No host synchronisation."""
+    _, _, H, W = pos.shape
+    N = H * W
+    bp = base_pos.float().reshape(1, 2, N).transpose(1, 2)
+    p, q_vis, q_score = dense_query(pos, score, bp)
+    s = base_score.float().reshape(1, N) + q_score
+    inf = torch.full_like(s, float("inf"))
+    vis = q_vis & (s < inf)
+    score_c = torch.where(vis, s, inf)
+    x, y = bp[..., 0], bp[..., 1]
+    zero = torch.zeros_like(x)
+    # visible: the base position is inside the frame, so the rounded one is a pixel; before any int conversion
+    cell = torch.round(torch.where(vis, y, zero)).long() * W + torch.round(torch.where(vis, x, zero)).long()
+    delta_c = torch.where(vis, delta.reshape(1, N).gather(1, cell), torch.full_like(delta.reshape(1, N), -1))
+    err_c = torch.where(vis, fb_err.float().reshape(1, N).gather(1, cell), inf)
+    return (p.transpose(1, 2).reshape(1, 2, H, W), score_c.reshape(1, 1, H, W), vis.reshape(1, 1, H, W),
+            delta_c.reshape(1, 1, H, W), err_c.reshape(1, 1, H, W))
+
+
 _SPLAT_HOLE = torch.iinfo(torch.int64).max
 
 

@@ -52,6 +52,12 @@ that have a covered cell within R cells with that cell's label
 (``ops.splat_inpaint``: csrc/splat_inpaint.hip on the GPU);
 ``covered_TTTT.png`` then holds 255 where a pixel lands, 128 where the label
 was in-painted and 0 at the holes that are left.
+
+``--dense --reanchor_every N`` / ``--reanchor_below F`` re-anchor the tracker on
+a later frame when the first one has drifted out of view (every N-th frame, or
+once fewer than the fraction F of the current anchor's pixels are visible;
+``DenseMultiFlowTracker.reanchor``).  Every file still describes ``0 -> t`` in
+the pixels of the first frame; without the options the files are unchanged.
 """
 import argparse
 import csv
@@ -127,7 +133,8 @@ def track_dense(args, model, images, pts, dev):
     in the directory --out, and with --points the eight-column CSV from query()."""
     from PIL import Image
     tracker = DenseMultiFlowTracker(model, iters=args.iters, deltas=_deltas(args.deltas), fb_alpha=tuple(args.fb_alpha),
-                                    warm_start=not args.no_warm_start, cache_features=args.cache_features)
+                                    warm_start=not args.no_warm_start, cache_features=args.cache_features,
+                                    reanchor_every=args.reanchor_every, reanchor_below=args.reanchor_below)
     os.makedirs(args.out, exist_ok=True)
     padder = InputPadder(load_image(images[0], dev).shape)
     shift = torch.tensor([padder._pad[0], padder._pad[2]], dtype=torch.float32, device=dev)
@@ -260,9 +267,20 @@ def parse_args(argv=None):
     parser.add_argument("--inpaint", type=_radius, default=0, metavar="R",
                         help="with --labels: fill holes from the nearest covered cell within R cells (an integer, or "
                              "'inf'); covered_TTTT.png then marks in-painted cells with 128")
+    parser.add_argument("--reanchor_every", type=int, metavar="N",
+                        help="with --dense: make every N-th frame the new anchor; the files still describe 0 -> t")
+    parser.add_argument("--reanchor_below", type=float, metavar="F",
+                        help="with --dense: re-anchor once fewer than this fraction (0 < F < 1) of the current anchor's "
+                             "pixels are visible; reads one scalar from the device per frame")
     args = parser.parse_args(argv)
     if args.dense and not args.deltas:
         parser.error("--dense needs --deltas")
+    if (args.reanchor_every is not None or args.reanchor_below is not None) and not args.dense:
+        parser.error("--reanchor_every and --reanchor_below need --dense")
+    if args.reanchor_every is not None and args.reanchor_every < 1:
+        parser.error("--reanchor_every needs a positive N")
+    if args.reanchor_below is not None and not 0.0 < args.reanchor_below < 1.0:
+        parser.error("--reanchor_below needs 0 < F < 1")
     if args.labels and not args.dense:
         parser.error("--labels needs --dense")
     if args.inpaint != 0 and not args.labels:
