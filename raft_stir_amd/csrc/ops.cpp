@@ -702,8 +702,9 @@ void wpack_gather(const Tensor& code, const Tensor& tab, const Tensor& out, at::
   check_gpu(tab, "tab");
   check_gpu(out, "out");
   TORCH_CHECK(code.scalar_type() == at::kInt && code.dim() == 1, "wpack_gather: code must be int32 [n]");
-  TORCH_CHECK(tab.scalar_type() == at::kLong && tab.dim() == 2 && tab.size(1) == 10 && tab.size(0) <= 128,
-              "wpack_gather: tab must be int64 [<=128][10]");
+  // the kernel decodes the row as (code >> 24) & 63
+  TORCH_CHECK(tab.scalar_type() == at::kLong && tab.dim() == 2 && tab.size(1) == 10 && tab.size(0) <= 64,
+              "wpack_gather: tab must be int64 [<=64][10]");
   TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat, "wpack_gather: out bf16/fp32");
   TORCH_CHECK(out.numel() == code.numel(), "wpack_gather: out / code size");
   TORCH_CHECK(rlo.size() == rhi.size() && rlo.size() == rs_.size() && rlo.size() <= 4, "wpack_gather: ranges");

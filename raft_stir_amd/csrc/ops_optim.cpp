@@ -24,13 +24,17 @@ using at::Tensor;
 // exp_avg_sq; partial: fp32 scratch of >= sum over groups of ceil(numel / CH)
 // floats; state: fp32 (completed steps, pending flag) -- see sumsq_kernel.
 // max_norm <= 0: no clipping.  Returns ||grads|| (fp32, 0-dim); a non-finite
-// norm leaves every parameter and moment unchanged.
+// norm leaves every parameter and moment unchanged.  Zero-element tensors are
+// checked and then left out of the launch groups (a group of them alone would
+// be a grid of 0 blocks and a second group with pbase == 0); with no element
+// at all nothing is launched, state is untouched and the norm is 0.
 Tensor clip_adamw(at::TensorList params, at::TensorList grads, const Tensor& exp_avg, const Tensor& exp_avg_sq,
                   const Tensor& partial, at::IntArrayRef moff, const c10::optional<Tensor>& lr_t, double lr,
                   double beta1, double beta2, double eps, double weight_decay, double max_norm, const Tensor& state) {
-  TORCH_CHECK(params.size() == grads.size() && params.size() == moff.size() && !params.empty(),
+  TORCH_CHECK(params.size() == grads.size() && params.size() == moff.size(),
               "clip_adamw_: params, grads and moff must have one entry per parameter");
-  const auto dev = params[0].device();
+  const auto dev = exp_avg.device();
+  TORCH_CHECK(dev.is_cuda(), "clip_adamw_: moments must be on the GPU");
   TORCH_CHECK(state.numel() == 2, "clip_adamw_: state must hold (steps, pending flag)");
   for (const Tensor* t : {&exp_avg, &exp_avg_sq, &partial, &state})
     TORCH_CHECK(t->device() == dev && t->scalar_type() == at::kFloat && t->is_contiguous(),
@@ -49,6 +53,7 @@ Tensor clip_adamw(at::TensorList params, at::TensorList grads, const Tensor& exp
                 "clip_adamw_: grad ", i, " must match its parameter's dtype, shape and dense strides");
     TORCH_CHECK(moff[i] >= 0 && moff[i] + p.numel() <= exp_avg.numel() && exp_avg_sq.numel() == exp_avg.numel(),
                 "clip_adamw_: moment offset out of range for parameter ", i);
+    if (p.numel() == 0) continue;
     if (groups.empty() || groups.back().n == rs::optim::MAXT) {
       if (!groups.empty()) pblocks += (groups.back().off[groups.back().n] + rs::optim::CH - 1) / rs::optim::CH;
       groups.emplace_back();
@@ -64,6 +69,7 @@ Tensor clip_adamw(at::TensorList params, at::TensorList grads, const Tensor& exp
     L.off[L.n + 1] = L.off[L.n] + p.numel();
     ++L.n;
   }
+  if (groups.empty()) return at::zeros({}, exp_avg.options());
   pblocks += (groups.back().off[groups.back().n] + rs::optim::CH - 1) / rs::optim::CH;
   TORCH_CHECK(partial.numel() >= pblocks, "clip_adamw_: partial scratch needs ", pblocks, " floats");
   Tensor norm = at::empty({}, exp_avg.options());

@@ -120,10 +120,11 @@ class FusedClipAdamW(optim.Optimizer):
     def state_dict(self):
         sd = super().state_dict()
         steps = float(self._state[0] + self._state[1])
-        for st in sd["state"].values():
-            st["step"] = torch.tensor(steps)
-            st["exp_avg"] = st["exp_avg"].clone()
-            st["exp_avg_sq"] = st["exp_avg_sq"].clone()
+        # the entries of sd["state"] ARE the live per-parameter dicts: fill copies, or the
+        # live exp_avg / exp_avg_sq stop being views of the flat buffers the kernel updates
+        # (and every later state_dict() would save the moments of the first one)
+        sd["state"] = {k: dict(st, step=torch.tensor(steps), exp_avg=st["exp_avg"].clone(),
+                               exp_avg_sq=st["exp_avg_sq"].clone()) for k, st in sd["state"].items()}
         return sd
 
     def load_state_dict(self, state_dict):
