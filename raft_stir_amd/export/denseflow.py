@@ -23,7 +23,11 @@ On a long sequence the tracker can be re-anchored on the current frame
 (:meth:`DenseMultiFlowTracker.reanchor`): the field so far is kept as a base and
 every later field is composed with it (ops.dense_compose,
 csrc/dense_compose.hip), so everything published stays indexed by the pixels of
-the first frame.
+the first frame.  Images move through the two maps by a bilinear backward warp
+(ops.backward_warp, csrc/backward_warp.hip): the current frame into the first
+frame's coordinates through ``pos`` (:meth:`DenseMultiFlowTracker.stabilize`),
+an image drawn on the first frame into the current one through ``inv_pos``
+(:meth:`DenseMultiFlowTracker.warp_image`).
 """
 from __future__ import annotations
 
@@ -271,6 +275,59 @@ class DenseMultiFlowTracker(MultiFlowTracker):
         got = lab.reshape(-1, H * W).index_select(1, src.reshape(-1).long().clamp_(min=0)).reshape(1, -1, H, W)
         hole = torch.full((), fill, dtype=lab.dtype, device=lab.device)
         return torch.where(covered if inpaint == 0 else src >= 0, got, hole).reshape(shape), covered
+
+    def _image(self, what, image):
+        """An image argument of stabilize() / warp_image(), checked, on the tracker's device."""
+        if self.pos is None:
+            raise ValueError(f"{what}() needs a step first")
+        H, W = self.pos.shape[-2:]
+        shape = tuple(image.shape)
+        if not (image.dim() == 4 and shape[0] == 1 and shape[1] >= 1 and shape[2:] == (H, W)):
+            raise ValueError(f"image must be (1,C,H,W) with H, W = {(H, W)}, got {shape}")
+        if image.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"image must be float32 or uint8, got {image.dtype}")
+        return image.to(self.pos.device)
+
+    @torch.no_grad()
+    def stabilize(self, image=None, fill=0):
+        """The current frame seen from the first one: a motion-compensated view.
+        image (1,C,H,W), fp32 or uint8, aligned with frame t (the frame itself,
+        or a second modality recorded with it); None: the current frame as the
+        tracker holds it, fp32 (on the GPU the static frame buffer,
+        channels-last, read in place) -> (stab (1,C,H,W) of the image's dtype:
+        at every pixel of frame 0 the image read bilinearly at the pixel's
+        position in frame t, ``fill`` where it is not ok; ok (1,1,H,W) bool:
+        the pixel is visible and its position is inside the frame).  This is
+        ``ops.backward_warp(image, pos, valid=visible, fill=fill)``
+        (csrc/backward_warp.hip on the GPU, an eager call on the current stream
+        after the step's replay, without a host synchronisation; the ATen
+        oracle on the CPU).  On the first frame it is the image itself.  ``pos``
+        stays indexed by the pixels of frame 0 through a re-anchor, so this
+        does too.  The tensors are the caller's own."""
+        from ..ops import backward_warp
+        if self.pos is None:
+            raise ValueError("stabilize() needs a step first")
+        image = self._st["frame"] if image is None else self._image("stabilize", image)
+        return backward_warp(image, self.pos, valid=self.visible, fill=fill)
+
+    @torch.no_grad()
+    def warp_image(self, image, footprint: int = 2, inpaint: int | None = 0, fill=0):
+        """Carry an image drawn on the first frame into the current one.
+        image (1,C,H,W), fp32 or uint8, in the coordinates of frame 0 ->
+        (warped (1,C,H,W) of the image's dtype, ok (1,1,H,W) bool): every cell
+        of frame t reads the image bilinearly at ``inv_pos``, the cell's
+        position in frame 0 that :meth:`splat` finds (``footprint`` and
+        ``inpaint`` are its arguments), not by nearest neighbour as
+        :meth:`warp_labels` does: ``ops.backward_warp(image, inv_pos,
+        fill=fill)``.  A hole of the splat (NaN ``inv_pos``), or an in-painted
+        cell whose rigid extension leaves the image, holds ``fill`` and is not
+        ok.  On the GPU two or three eager calls on the current stream after the
+        step's replay, without a host synchronisation.  The tensors are the
+        caller's own."""
+        from ..ops import backward_warp
+        image = self._image("warp_image", image)
+        inv_pos = self.splat(None, footprint=footprint, inpaint=inpaint)[2]
+        return backward_warp(image, inv_pos, fill=fill)
 
     @torch.no_grad()
     def track(self, frames, labels=None, footprint: int = 2, fill=0, inpaint: int | None = 0):

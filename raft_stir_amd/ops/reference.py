@@ -457,6 +457,56 @@ def dense_compose(base_pos, base_score, pos, score, delta, fb_err):
             delta_c.reshape(1, 1, H, W), err_c.reshape(1, 1, H, W))
 
 
+def backward_warp(image, coords, valid=None, fill=0):
+    """Backward warp of an image through a field of positions: every cell of
+    the output reads the image bilinearly at its position.  This docstring is
+    the rule.  image (1,C,Hs,Ws) fp32 or uint8, of any layout; coords
+    (1,2,H,W), xy positions in the image ((H,W) need not be (Hs,Ws)); valid
+    (1,1,H,W) bool or None; fill a float (fp32) or an integer in [0,255]
+    (uint8) -> (warped (1,C,H,W) of the image's dtype, ok (1,1,H,W) bool).
+
+    ok      ``valid`` (if given) AND inside(x, y): 0 <= x <= Ws-1 and
+            0 <= y <= Hs-1, decided on the floats (NaN, infinities, 1e30 fail).
+    taps    (floor x + {0,1}, floor y + {0,1}) in the order (0,0), (1,0),
+            (0,1), (1,1); a weight is one fp32 product of (1 - wx | wx) and
+            (1 - wy | wy).  A tap of weight 0, or at column Ws or row Hs, is
+            never read: a NaN or an infinity of the image cannot pass through
+            a weight of 0.
+    sample  per channel u = 0; u = u + w * f[i] per tap read, every product
+            and every sum rounded once (no FMA); a uint8 value is converted to
+            fp32 first, exactly.  At an integer point this is the stored value
+            (a stored -0.0 reads as +0.0: 0 + -0 is +0).
+    store   fp32: u.  uint8: clamp(rint(u), 0, 255), halves to even.  A cell
+            that is not ok holds ``fill`` in every channel.
+
+    The sampling rule is dense_query's (csrc/query_device.h).  No host
+    synchronisation."""
+    _, C, Hs, Ws = image.shape
+    _, _, H, W = coords.shape
+    N = H * W
+    p = coords.float().reshape(2, N)
+    x, y = p[0], p[1]
+    inside = (x >= 0) & (x <= Ws - 1) & (y >= 0) & (y <= Hs - 1)  # NaN fails
+    ok = inside if valid is None else inside & valid.reshape(N)
+    zero = torch.zeros_like(x)
+    xs, ys = torch.where(inside, x, zero), torch.where(inside, y, zero)  # before any int conversion
+    x0, y0 = torch.floor(xs), torch.floor(ys)
+    wx, wy = xs - x0, ys - y0
+    ux, uy = 1 - wx, 1 - wy
+    xi0, yi0 = x0.long(), y0.long()
+    flat = image.reshape(C, Hs * Ws)
+    u = torch.zeros(C, N, dtype=torch.float32, device=image.device)
+    for dx, dy, w in ((0, 0, ux * uy), (1, 0, wx * uy), (0, 1, ux * wy), (1, 1, wx * wy)):
+        xi, yi = xi0 + dx, yi0 + dy
+        use = (w != 0) & (xi < Ws) & (yi < Hs)
+        val = flat.index_select(1, yi.clamp(0, Hs - 1) * Ws + xi.clamp(0, Ws - 1)).float()
+        u = torch.where(use, u + w * val, u)
+    if image.dtype == torch.uint8:
+        u = torch.round(u).clamp(0, 255).to(torch.uint8)
+    warped = torch.where(ok, u, torch.full_like(u, fill))
+    return warped.reshape(1, C, H, W), ok.reshape(1, 1, H, W)
+
+
 _SPLAT_HOLE = torch.iinfo(torch.int64).max
 
 

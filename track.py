@@ -6,7 +6,7 @@ whole sequence, with RAFT's video warm start).
         [--fb_check [--fb_alpha A1 A2]] [--deltas 1 4 16 inf] [--cache_features] \
         --path demo-frames --points points.txt --out tracks.csv
     python track.py --model M --dense --deltas 1 4 16 inf [--points points.txt] [--labels mask.png [--inpaint R]] \
-        --path demo-frames --out tracks/
+        [--stabilize] [--overlay image.png] --path demo-frames --out tracks/
 
 ``points.txt`` holds one ``x y`` per line, in pixels of the first frame.  The
 CSV has a ``frame,point,x,y`` row for every point in every frame (frame 0 holds
@@ -58,6 +58,21 @@ a later frame when the first one has drifted out of view (every N-th frame, or
 once fewer than the fraction F of the current anchor's pixels are visible;
 ``DenseMultiFlowTracker.reanchor``).  Every file still describes ``0 -> t`` in
 the pixels of the first frame; without the options the files are unchanged.
+
+``--dense --stabilize`` writes per frame t ``stab_TTTT.png``, 8-bit RGB: frame t
+in the first frame's coordinates, every pixel of the first frame showing what
+frame t holds where the pixel went (``DenseMultiFlowTracker.stabilize`` on the
+8-bit frame: ``ops.backward_warp``, csrc/backward_warp.hip on the GPU), cropped
+back from the padding, 0 where the pixel is not visible or has left the frame.
+
+``--dense --overlay image.png`` takes an 8-bit image of 1, 3 or 4 channels in
+the first frame's size (an annotation, a colour overlay; an alpha channel is
+warped like the others), pads it with 0 like ``--labels`` and writes per frame
+t ``overlay_TTTT.png``: the image carried into frame t, read bilinearly through
+the inverse map of the splat (``DenseMultiFlowTracker.warp_image``), which
+honours ``--splat_footprint`` and ``--inpaint``; 0 where no pixel of the first
+frame lands.  Only what is written goes to the host; without the two options
+every other file is unchanged.
 """
 import argparse
 import csv
@@ -150,9 +165,32 @@ def track_dense(args, model, images, pts, dev):
                              f"{mask.shape}")
         # the padding carries label 0, not a replicated border
         labels = torch.nn.functional.pad(torch.from_numpy(mask.astype(np.int32)), padder._pad, value=0).to(dev)
+    overlay = None
+    if args.overlay:
+        img = np.asarray(Image.open(args.overlay))
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3, 4)):
+            raise ValueError(f"{args.overlay}: an 8-bit PNG of 1, 3 or 4 channels expected, got {img.dtype} "
+                             f"{img.shape}")
+        if img.shape[:2] != (padder.ht, padder.wd):
+            raise ValueError(f"{args.overlay}: the first frame's size {(padder.ht, padder.wd)} expected, got "
+                             f"{img.shape[:2]}")
+        # (1,C,H,W); the padding is 0 (transparent where there is an alpha channel), not a replicated border
+        chw = torch.from_numpy(img.reshape(padder.ht, padder.wd, -1).copy()).permute(2, 0, 1)
+        overlay = torch.nn.functional.pad(chw, padder._pad, value=0)[None].contiguous().to(dev)
     cols = [[], [], [], [], []]
     for t, f in enumerate(images):
-        tracker.step(padder.pad(load_image(f, dev))[0])
+        frame = padder.pad(load_image(f, dev))[0]
+        tracker.step(frame)
+        if args.stabilize:
+            # on the 8-bit frame (the values are integers: the conversion is exact), so the file is the uint8 rule's
+            stab, _ = tracker.stabilize(frame.to(torch.uint8), fill=0)
+            stab = padder.unpad(stab)[0].permute(1, 2, 0).cpu().numpy()
+            Image.fromarray(stab).save(os.path.join(args.out, f"stab_{t:04d}.png"))
+        if overlay is not None:
+            moved, _ = tracker.warp_image(overlay, footprint=args.splat_footprint, inpaint=args.inpaint, fill=0)
+            moved = padder.unpad(moved)[0].permute(1, 2, 0).cpu().numpy()
+            Image.fromarray(moved[..., 0] if moved.shape[2] == 1 else moved).save(
+                os.path.join(args.out, f"overlay_{t:04d}.png"))
         if labels is not None:
             # splatted where the field is; only what is written goes to the host
             if args.inpaint == 0:
@@ -184,6 +222,10 @@ def track_dense(args, model, images, pts, dev):
     print(f"wrote {len(images)} flow fields and visibility maps to {args.out}")
     if labels is not None:
         print(f"wrote {len(images)} warped label images and coverage maps to {args.out}")
+    if args.stabilize:
+        print(f"wrote {len(images)} stabilised frames to {args.out}")
+    if overlay is not None:
+        print(f"wrote {len(images)} warped overlays to {args.out}")
     if points is None:
         return None
     traj, err, vis, score, delta = (torch.cat(c).cpu().numpy() for c in cols)
@@ -263,10 +305,16 @@ def parse_args(argv=None):
                         help="with --dense: an 8- or 16-bit single-channel label image of the first frame; every "
                              "frame's labels_TTTT.png and covered_TTTT.png go into the directory --out")
     parser.add_argument("--splat_footprint", type=int, choices=(1, 2), default=2,
-                        help="with --labels: a pixel claims its nearest cell (1) or every cell it touches (2)")
+                        help="with --labels / --overlay: a pixel claims its nearest cell (1) or every cell it touches "
+                             "(2)")
     parser.add_argument("--inpaint", type=_radius, default=0, metavar="R",
-                        help="with --labels: fill holes from the nearest covered cell within R cells (an integer, or "
-                             "'inf'); covered_TTTT.png then marks in-painted cells with 128")
+                        help="with --labels / --overlay: fill holes from the nearest covered cell within R cells (an "
+                             "integer, or 'inf'); covered_TTTT.png then marks in-painted cells with 128")
+    parser.add_argument("--stabilize", action="store_true",
+                        help="with --dense: write every frame in the first frame's coordinates as stab_TTTT.png")
+    parser.add_argument("--overlay", metavar="IMAGE.png",
+                        help="with --dense: an 8-bit image of 1, 3 or 4 channels on the first frame; it is carried "
+                             "into every frame as overlay_TTTT.png (honours --splat_footprint and --inpaint)")
     parser.add_argument("--reanchor_every", type=int, metavar="N",
                         help="with --dense: make every N-th frame the new anchor; the files still describe 0 -> t")
     parser.add_argument("--reanchor_below", type=float, metavar="F",
@@ -283,8 +331,10 @@ def parse_args(argv=None):
         parser.error("--reanchor_below needs 0 < F < 1")
     if args.labels and not args.dense:
         parser.error("--labels needs --dense")
-    if args.inpaint != 0 and not args.labels:
-        parser.error("--inpaint needs --labels")
+    if (args.stabilize or args.overlay) and not args.dense:
+        parser.error("--stabilize and --overlay need --dense")
+    if args.inpaint != 0 and not (args.labels or args.overlay):
+        parser.error("--inpaint needs --labels or --overlay")
     if not args.dense and not args.points:
         parser.error("the following arguments are required: --points")
     return args
